@@ -21,7 +21,14 @@ halo-subgraph semantics of graph_op.cc:403-509 with num_hops = 1) and holds
 the source features replicated (DESIGN.md "Multi-GPU"), so the timed SpMM
 has no data-path collective.  `value` = all ranks' edges / max-over-ranks time.
 
-cpu_baseline: the reference's CPU algorithm (out-CSR traversal, OpenMP over
+A plain run (`--gpus N --steps K --warmup W`) builds the workload, warms up, times
+the K steps and prints the headline line; `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  Everything else -- the workload's
+correctness checks, the rocprofv3 PMC passes, the stream-copy probe, update_all,
+the CPU baseline, the with-exchange / C4 / C5 lines, the C2 / C3 / C5 configs --
+runs only with `--full`.
+
+cpu_baseline (`--full`): the reference's CPU algorithm (out-CSR traversal, OpenMP over
 source rows, `omp atomic` scatter; oracle/dgl_ref.c) on a bounded sample of
 the same graph, rank 0 at N = 1 only.
 """
@@ -1345,11 +1352,86 @@ def job_roofline(per_rank, world):
     return roof, egress
 
 
+def check_workload(gidx, x, out, n, n_dst, dist, cdev, device):
+    """Correctness spot check on the resident workload (``--full``): a checksum of
+    checksums is order-independent up to fp32 rounding (sum over rows of out ==
+    sum_u outdeg(u) * X[u]); then 4096 random rows recomputed with torch gathers (fp64)."""
+    outdeg = th.bincount(gidx.in_csr.indices.long(), minlength=n).double()
+    expect = th.zeros(FEAT, dtype=th.float64, device=device)
+    for lo in range(0, n, 1 << 22):  # chunked: x.double() of a 2^26-row table is 34 GB
+        hi = min(n, lo + (1 << 22))
+        expect += (outdeg[lo:hi, None] * x[lo:hi].double()).sum(0)
+    got = out.double().sum(0)
+    rel = float(((got - expect).abs().max() / expect.abs().max().clamp(min=1)).item())
+    rel = _max_over_ranks(rel, dist, cdev)
+    log("checksum-of-checksums rel err %.2e (max over ranks)" % rel)
+    if rel > 1e-3:
+        raise SystemExit("copy_u_sum checksum mismatch: %g" % rel)
+    del outdeg, expect, got
+    gen = th.Generator(device=device)
+    gen.manual_seed(7)
+    rows = th.randint(0, n_dst, (4096,), generator=gen, device=device)
+    ip = gidx.in_csr.indptr.long()
+    beg, end = ip[rows], ip[rows + 1]
+    lens = end - beg
+    seg = th.repeat_interleave(th.arange(4096, device=device), lens)
+    pos = (th.repeat_interleave(beg - th.cumsum(lens, 0) + lens, lens)
+           + th.arange(int(lens.sum()), device=device))
+    cols = gidx.in_csr.indices.long()[pos]
+    xr = x.double()[cols]
+    exact = th.zeros(4096, FEAT, dtype=th.float64, device=device).index_add_(0, seg, xr)
+    mass = th.zeros(4096, FEAT, dtype=th.float64, device=device).index_add_(0, seg, xr.abs())
+    err = (out[rows].double() - exact).abs()
+    bad = _max_over_ranks(float((err > 1e-4 + 1e-6 * mass).any()), dist, cdev)
+    if bad > 0:
+        raise SystemExit("copy_u_sum row check failed: max err %g" % float(err.max()))
+    log("row spot check (4096 rows, fp64 torch gathers): max abs err %.2e" % float(err.max()))
+
+
+# rows of the timed step's output that --dump-outputs keeps (x FEAT fp32 = 32 MiB), all ranks
+DUMP_ROWS = 131072
+
+
+def dump_sample_rows(n_rows, keep):
+    """The rows of an n_rows-row output that --dump-outputs writes: all of them when
+    they fit, else a fixed seeded sample, ascending."""
+    if n_rows <= keep:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(20231).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(directory, out, world, rank):
+    """``--dump-outputs DIR``: what the last timed step left in ``out`` (the array a
+    caller of copy_u_sum receives), for comparing two builds output for output:
+    ``out_rows.npy`` -- fp32 rows of it (dump_sample_rows) -- and ``out_colsum.npy``
+    -- the fp64 column sums over ALL its rows, so no row escapes.  At N > 1 every
+    rank writes its own row block's pair with a ``.rank<r>`` infix."""
+    os.makedirs(directory, exist_ok=True)
+    tag = "" if world == 1 else ".rank%d" % rank
+    rows = dump_sample_rows(int(out.shape[0]), DUMP_ROWS // world)
+    idx = th.from_numpy(rows).to(out.device)
+    np.save(os.path.join(directory, "out_rows%s.npy" % tag),
+            out.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False))
+    colsum = th.zeros(out.shape[1], dtype=th.float64, device=out.device)
+    for lo in range(0, int(out.shape[0]), 1 << 22):
+        colsum += out[lo:lo + (1 << 22)].double().sum(0)
+    np.save(os.path.join(directory, "out_colsum%s.npy" % tag), colsum.cpu().numpy())
+    log("outputs of the last timed step written to %s" % directory)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the workload's correctness checks, the rocprofv3 "
+                         "PMC passes, the stream-copy probe, update_all, the CPU baseline, the "
+                         "with-exchange / C4 / C5 lines and the C2 / C3 / C5 configs (each can be "
+                         "left out with its --no-... option); a plain run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     # rehearsal knobs (small graphs, gloo collectives with every rank on one GPU);
     # the headline run uses the defaults
@@ -1394,6 +1476,9 @@ def main():
     if args.gpus < 1:
         log("--gpus must be >= 1")
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        log("--steps must be >= 1 and --warmup >= 0")
+        return 2
     if args.same_device and args.gpus >= 3 and not same_device_small(args):
         # three or more processes on one GPU crawl inside rocPRIM's
         # decoupled-look-back sorts at full size (partition_stats 180 s per rank at
@@ -1417,7 +1502,7 @@ def main():
     pmc = None
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ)
     local = 0 if args.same_device else int(os.environ.get("LOCAL_RANK", "0"))
-    if not args.no_pmc and not under_profiler:
+    if args.full and not args.no_pmc and not under_profiler:
         # counters first, in child processes on this rank's own GPU, before this
         # process touches the GPU (every rank measures its own launch pair)
         t0 = time.time()
@@ -1449,7 +1534,7 @@ def main():
     th.cuda.synchronize()
     log("CSRs built on device in %.2fs" % (time.time() - t0))
     part = None
-    if world > 1 and not args.no_exchange:
+    if world > 1 and args.full and not args.no_exchange:
         # the same rows planned as a halo partition (owned X rows + halo rows
         # fetched by one all-to-all-v per step), for the with-exchange line
         from dgl import distributed as D
@@ -1461,7 +1546,7 @@ def main():
         log("halo plan built on device in %.2fs: %d halo rows on rank 0"
             % (time.time() - t0, part.n_halo))
     upd = None
-    if world == 1 and not args.no_update_all:
+    if world == 1 and args.full and not args.no_update_all:
         import dgl
         upd = dgl.DGLGraph.from_device_coo(src, dst, n)
     del src, dst
@@ -1471,41 +1556,10 @@ def main():
     def step():
         K.copy_reduce("sum", gidx, 0, x, out)
 
-    # correctness spot check on the resident workload: a checksum of checksums is
-    # order-independent up to fp32 rounding (sum over rows of out == sum_u outdeg(u) * X[u])
     step()
     th.cuda.synchronize()
-    outdeg = th.bincount(gidx.in_csr.indices.long(), minlength=n).double()
-    expect = th.zeros(FEAT, dtype=th.float64, device=device)
-    for lo in range(0, n, 1 << 22):  # chunked: x.double() of a 2^26-row table is 34 GB
-        hi = min(n, lo + (1 << 22))
-        expect += (outdeg[lo:hi, None] * x[lo:hi].double()).sum(0)
-    got = out.double().sum(0)
-    rel = float(((got - expect).abs().max() / expect.abs().max().clamp(min=1)).item())
-    rel = _max_over_ranks(rel, dist, cdev)
-    log("checksum-of-checksums rel err %.2e (max over ranks)" % rel)
-    if rel > 1e-3:
-        raise SystemExit("copy_u_sum checksum mismatch: %g" % rel)
-    del outdeg, expect, got
-    # row-exact spot check: 4096 random rows recomputed with torch gathers (fp64)
-    gen = th.Generator(device=device)
-    gen.manual_seed(7)
-    rows = th.randint(0, n_dst, (4096,), generator=gen, device=device)
-    ip = gidx.in_csr.indptr.long()
-    beg, end = ip[rows], ip[rows + 1]
-    lens = end - beg
-    seg = th.repeat_interleave(th.arange(4096, device=device), lens)
-    pos = th.repeat_interleave(beg - th.cumsum(lens, 0) + lens, lens) + th.arange(int(lens.sum()), device=device)
-    cols = gidx.in_csr.indices.long()[pos]
-    xr = x.double()[cols]
-    exact = th.zeros(4096, FEAT, dtype=th.float64, device=device).index_add_(0, seg, xr)
-    mass = th.zeros(4096, FEAT, dtype=th.float64, device=device).index_add_(0, seg, xr.abs())
-    err = (out[rows].double() - exact).abs()
-    bad = _max_over_ranks(float((err > 1e-4 + 1e-6 * mass).any()), dist, cdev)
-    if bad > 0:
-        raise SystemExit("copy_u_sum row check failed: max err %g" % float(err.max()))
-    log("row spot check (4096 rows, fp64 torch gathers): max abs err %.2e" % float(err.max()))
-    del seg, pos, cols, xr, exact, mass, err
+    if args.full:
+        check_workload(gidx, x, out, n, n_dst, dist, cdev, device)
 
     for _ in range(args.warmup):
         step()
@@ -1527,7 +1581,9 @@ def main():
     elapsed = time.perf_counter() - t_start
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     edges_total = m_local
-    if pmc is None and m1:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
+    if pmc is None and m1 and args.full:
         # no live counters (profiler unavailable, or this run is itself under
         # rocprofv3): the committed passes of the same launch at this head
         try:
@@ -1608,6 +1664,15 @@ def main():
         "hbm_gbps_bounds": [roof["compulsory_GBps"], egress],
         "edges_per_sec_per_gpu": value / world,
     }
+    if not args.full:
+        # a plain run: the headline line alone (its roofline from the timed steps' own
+        # HIP events and the bytes models; no counters, probes, baselines or side lines)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     try:
         peak = stream_copy_peak(device)
         res["roofline"]["measured_stream_copy_GBps"] = peak

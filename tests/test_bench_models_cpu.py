@@ -101,3 +101,26 @@ def test_job_roofline_aggregates_over_the_slowest_rank():
     roof2, eg2 = bench.job_roofline([_rec(0, 2.0, 30e9, 14e9), _rec(1, 2.0, 30e9, None)], 2)
     assert eg2 is None and roof2["traffic"] is None and roof2["hbm_frac_bounds"] is None
     assert roof2["frac"] == pytest.approx(30000.0 / 16000.0)
+
+
+def test_dump_outputs_writes_a_fixed_sample_and_the_column_sums(tmp_path):
+    """--dump-outputs: a small output goes out whole, a large one as the same seeded rows
+    on every call (ascending, distinct, inside the byte budget); the column sums cover
+    every row; at N > 1 each rank writes its own pair."""
+    import numpy as np
+    import torch as th
+    rows = bench.dump_sample_rows(10, 16)
+    assert rows.tolist() == list(range(10))
+    big = bench.dump_sample_rows(1 << 23, bench.DUMP_ROWS)
+    assert big.shape == (bench.DUMP_ROWS,) and (np.diff(big) > 0).all()
+    assert big[0] >= 0 and big[-1] < 1 << 23
+    assert np.array_equal(big, bench.dump_sample_rows(1 << 23, bench.DUMP_ROWS))
+    assert bench.DUMP_ROWS * bench.FEAT * 4 + bench.FEAT * 8 <= 64 * 1000 * 1000
+    out = th.arange(40 * bench.FEAT, dtype=th.float32).reshape(40, bench.FEAT)
+    bench.dump_outputs(str(tmp_path / "a"), out, 1, 0)
+    got = np.load(tmp_path / "a" / "out_rows.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy())
+    cs = np.load(tmp_path / "a" / "out_colsum.npy")
+    assert cs.dtype == np.float64 and np.array_equal(cs, out.double().sum(0).numpy())
+    bench.dump_outputs(str(tmp_path / "b"), out, 2, 1)
+    assert sorted(os.listdir(tmp_path / "b")) == ["out_colsum.rank1.npy", "out_rows.rank1.npy"]
