@@ -399,6 +399,34 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
   if (kind == FAST_COL_MUL_EDGE_BCAST && !a.eids && head_dim == F && w_map == nullptr &&
       red == RED_SUM)
     kind = FAST_COL_MUL_POS;
+  // hub plan: the same launch over the plan's walk (virtual rows first), hub rows' partials
+  // in a scratch table of their own (not the carry workspace) and merged after the fixup
+  const DGLMIHubPlan* plan = &walk == &g->in_csr ? g->in_hub_plan
+                             : (&walk == &g->out_csr ? g->out_hub_plan : nullptr);
+  if (plan != nullptr && !(kind == FAST_COPY_COL && red == RED_SUM && x_map == nullptr && epi == nullptr &&
+                           !wide(g) && fast_marked_supported(F) && plan->num_hubs > 0))
+    plan = nullptr;
+  DGLMIGraph no_ws;
+  std::memset(&no_ws, 0, sizeof(no_ws));
+  const int64_t virt = plan ? plan->num_blocks * plan->num_hubs : 0;
+  Scratch part(&no_ws, virt * F * static_cast<int64_t>(sizeof(float)), s);
+  if (plan != nullptr) {
+    DGLMI_CHECK(plan->nnz == walk.nnz && plan->hub_nnz <= walk.nnz && plan->num_blocks >= 1 &&
+                    plan->rows && plan->indices && plan->indptr && plan->hub_rows,
+                "hub plan does not belong to this CSR");
+    a.indptr = IdxPtr{plan->indptr, 0};
+    a.rows = plan->rows;
+    a.indices = plan->marked ? plan->marked : plan->indices;
+    a.marked = plan->marked != nullptr;
+    a.num_cols = walk.num_cols;
+    a.num_rows = virt + walk.num_rows;
+    a.part = static_cast<float*>(part.ptr);
+    a.virt_rows = virt;
+    a.hub_rows = plan->hub_rows;
+    a.num_hubs = plan->num_hubs;
+    a.hub_blocks = plan->num_blocks;
+    a.hub_nnz = plan->hub_nnz;
+  }
   Scratch carry(g, fast_workspace_bytes(walk.nnz, F), s);
   a.carry = static_cast<float*>(carry.ptr);
   a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(carry.ptr) + fast_carry_bytes(walk.nnz, F));

@@ -333,6 +333,18 @@ struct FastArgs {
   int marked;
   const float* xr;      // FAST_COL_TIE: the reduce's input, one row per walk row
   int64_t num_cols;     // rows of the gathered table (policy-probe bound check)
+  // hub plan (DGLMIHubPlan; part != null): rows / indices / indptr are the plan's walk of
+  // virt_rows virtual rows (hub row h's edges from source block b: row b * num_hubs + h)
+  // followed by the real rows shifted by virt_rows.  A finished virtual row lands raw in
+  // part (virt_rows x F), a real row r in out[r - virt_rows]; the merge kernel then sums
+  // every hub row's hub_blocks partials, in block order, into out[hub_rows[h]].
+  float* part;
+  int64_t virt_rows;
+  const int32_t* hub_rows;
+  int64_t num_hubs;
+  int64_t hub_blocks;
+  int64_t hub_nnz;      // positions of the virtual rows (the plan's first part)
+  int64_t plan_wgs;     // workgroups remapped to their XCD's source block (a multiple of 8)
 };
 int64_t fast_chunk_edges(int64_t nnz, int64_t F);
 int64_t fast_workspace_bytes(int64_t nnz, int64_t F);  // carries + counters

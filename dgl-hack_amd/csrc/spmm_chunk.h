@@ -204,8 +204,22 @@ __device__ __forceinline__ typename VecT<VW>::T epiv(const FastArgs& a, typename
   return v;
 }
 
-template <int KIND, int RED, int L, int NV, int VAR = 3, bool EPI = false, int VW = 4>
+// Where a finished row lands.  PLAN (the hub plan's walk, FastArgs.part): virtual rows in
+// the partial table, real rows -- numbered after the virtual ones -- in out.
+template <bool PLAN>
+__device__ __forceinline__ float* row_dst(const FastArgs& a, int64_t r) {
+  if constexpr (PLAN) return r < a.virt_rows ? a.part + r * a.F : a.out + (r - a.virt_rows) * a.F;
+  else return a.out + r * a.F;
+}
+
+// PLAN: the first a.plan_wgs workgroups (a multiple of 8) walk the hub part, whose
+// positions are sorted by source block.  Workgroups b and b + 8 run on the same XCD, so
+// workgroup bid takes chunk group (bid % 8) * (plan_wgs / 8) + bid / 8: each XCD walks one
+// contiguous eighth of the hub part and its L2 keeps one source block instead of a copy of
+// every block's hottest rows.  Placement only: any mapping computes the same bits.
+template <int KIND, int RED, int L, int NV, int VAR = 3, bool EPI = false, int VW = 4, bool PLAN = false>
 __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indptr) {
+  static_assert(!PLAN || !EPI, "the plan variant has no epilogue");
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront (fill_empty_rows)");
   constexpr int G = kBlock / L;           // groups per block
   constexpr int B = (L > 16 ? L : 16) * ((VAR & 4) ? 2 : 1);  // positions staged per step
@@ -222,7 +236,11 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
 
   const int g = threadIdx.x / L;
   const int lane = threadIdx.x % L;
-  const int64_t chunk = (int64_t)blockIdx.x * G + g;
+  int64_t bid = blockIdx.x;
+  if constexpr (PLAN) {
+    if (bid < a.plan_wgs) bid = (bid % 8) * (a.plan_wgs / 8) + bid / 8;
+  }
+  const int64_t chunk = bid * G + g;
   const int64_t K = a.chunk;
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;  // whole group exits together
@@ -376,7 +394,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
         if (r == INT_MAX) break;
         if (r != cur) {
           // flush the finished row (empty rows in between: fill_empty_rows)
-          float* dst = cont ? a.carry + chunk * a.F : a.out + cur * a.F;
+          float* dst = cont ? a.carry + chunk * a.F : row_dst<PLAN>(a, cur);
 #pragma unroll
           for (int v = 0; v < NV; ++v) {
             const int f4 = lane + v * L;
@@ -405,7 +423,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
     __builtin_amdgcn_wave_barrier();
   }
   {
-    float* dst = cont ? a.carry + chunk * a.F : a.out + cur * a.F;
+    float* dst = cont ? a.carry + chunk * a.F : row_dst<PLAN>(a, cur);
     // a row that goes on in the next chunk stays raw: the fixup finishes it
     const bool done = !cont && !(EPI && p1 < a.nnz && a.rows[p1] == cur);
 #pragma unroll
@@ -418,7 +436,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int f4 = lane + v * L;
-      if (f4 < F4) st_out<VAR>(a.out + r * a.F + VW * f4, epiv<EPI, VW>(a, I, r, f4));
+      if (f4 < F4) st_out<VAR>(row_dst<PLAN>(a, r) + VW * f4, epiv<EPI, VW>(a, I, r, f4));
     }
   });
 }
@@ -428,7 +446,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
 // work, or -- for rows of more than kFixSeg continuation chunks, when the
 // workspace has counters -- every kFixSeg-th one folds a segment and the last
 // to finish folds the head and the segment partials (internal.h).
-template <int RED, int L, int NV, bool EPI = false, int VW = 4>
+template <int RED, int L, int NV, bool EPI = false, int VW = 4, bool PLAN = false>
 __global__ void __launch_bounds__(kBlock) k_chunk_fixup(FastArgs a, IdxPtr indptr) {
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront (seg_arrive_last)");
   constexpr int G = kBlock / L;
@@ -487,15 +505,32 @@ __global__ void __launch_bounds__(kBlock) k_chunk_fixup(FastArgs a, IdxPtr indpt
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const int f4 = lane + v * L;
-    acc[v] = f4 < F4 ? vld<VW>(a.out + r * a.F + VW * f4) : vident<VW, RED>();
+    acc[v] = f4 < F4 ? vld<VW>(row_dst<PLAN>(a, r) + VW * f4) : vident<VW, RED>();
   }
   if (nseg > 1) fold(acc, first, first + (nseg - 1) * kFixSeg, kFixSeg);
   else fold(acc, first, last, 1);
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const int f4 = lane + v * L;
-    if (f4 < F4) vst(a.out + r * a.F + VW * f4, epiv<EPI, VW>(a, acc[v], r, f4));
+    if (f4 < F4) vst(row_dst<PLAN>(a, r) + VW * f4, epiv<EPI, VW>(a, acc[v], r, f4));
   }
+}
+
+// The hub plan's last step (after the fixup, whose name it carries: the benchmark's
+// counter tally tells a step's kernels apart by name): out[hub_rows[h]] = the sum over
+// source blocks b, in block order, of the partial rows part[b * num_hubs + h].  One group
+// of L lanes per hub row, one float4 per lane.
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_chunk_fixup_merge(FastArgs a) {
+  constexpr int G = kBlock / L;
+  const int64_t h = (int64_t)blockIdx.x * G + threadIdx.x / L;
+  const int f4 = threadIdx.x % L;
+  if (h >= a.num_hubs || f4 >= a.F / 4) return;
+  const float* p = a.part + h * a.F + 4 * f4;
+  const int64_t step = a.num_hubs * a.F;
+  float4 acc = ld4(p);
+  for (int64_t b = 1; b < a.hub_blocks; ++b) acc = vadd(acc, ld4(p + b * step));
+  st4(a.out + static_cast<int64_t>(a.hub_rows[h]) * a.F + 4 * f4, acc);
 }
 
 
@@ -546,6 +581,22 @@ void run(const FastArgs& a, IdxPtr indptr, hipStream_t s) {
   const int64_t chunks = (a.nnz + a.chunk - 1) / a.chunk;
   const unsigned blocks = static_cast<unsigned>((chunks + G - 1) / G);
   if constexpr (KIND == FAST_COPY_COL && RED == RED_SUM && NV == 1 && L >= 16 && VW == 4) {
+    if (a.part != nullptr) {  // hub plan (capi.cpp run_fast decides; never with an epilogue)
+      FastArgs p = a;
+      p.plan_wgs = (a.hub_nnz / a.chunk / G) & ~int64_t(7);
+      if (a.marked)
+        hipLaunchKernelGGL((k_chunk_reduce<KIND, RED, L, NV, 11, false, VW, true>), dim3(blocks),
+                           dim3(kBlock), 0, s, p, indptr);
+      else
+        hipLaunchKernelGGL((k_chunk_reduce<KIND, RED, L, NV, 3, false, VW, true>), dim3(blocks),
+                           dim3(kBlock), 0, s, p, indptr);
+      if (chunks > 1)
+        hipLaunchKernelGGL((k_chunk_fixup<RED, L, NV, false, VW, true>), dim3(blocks), dim3(kBlock),
+                           0, s, p, indptr);
+      hipLaunchKernelGGL((k_chunk_fixup_merge<L>), dim3(static_cast<unsigned>((a.num_hubs + G - 1) / G)),
+                         dim3(kBlock), 0, s, p);
+      return;
+    }
     if (a.marked) {  // cold-row hints present (capi.cpp run_fast decides)
 #if DGLMI_PROBES
       const int pol = spmm_policy();

@@ -51,6 +51,23 @@ class Graph(ctypes.Structure):
         ("gat_edge_pos", ctypes.c_void_p),
         ("etypes", ctypes.c_void_p),
         ("eid_identity", ctypes.c_int32),
+        ("in_hub_plan", ctypes.c_void_p),
+        ("out_hub_plan", ctypes.c_void_p),
+    ]
+
+
+class HubPlan(ctypes.Structure):
+    """DGLMIHubPlan (include/dglmi.h)."""
+    _fields_ = [
+        ("num_blocks", ctypes.c_int32),
+        ("num_hubs", ctypes.c_int64),
+        ("hub_nnz", ctypes.c_int64),
+        ("nnz", ctypes.c_int64),
+        ("rows", ctypes.c_void_p),
+        ("indices", ctypes.c_void_p),
+        ("marked", ctypes.c_void_p),
+        ("indptr", ctypes.c_void_p),
+        ("hub_rows", ctypes.c_void_p),
     ]
 
 

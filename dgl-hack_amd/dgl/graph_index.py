@@ -79,6 +79,45 @@ class DeviceCSR:
         return self._deg
 
 
+def build_hub_plan(indptr, indices, rows, hub_degree, nb=8):
+    """The hub plan of a CSR (DGLMIHubPlan, include/dglmi.h) with torch ops on the CSR's
+    device (CPU tensors work too): rows of degree >= ``hub_degree`` are hubs; their
+    positions come first, sorted by (source block, hub, original position) under the
+    virtual row ``block * num_hubs + hub``, then every other position in CSR order under
+    ``nb * num_hubs + row``.  Source blocks are contiguous column-id ranges cut at the
+    1 / nb quantiles of the hub positions' columns (a column never straddles two blocks,
+    so block sizes differ from equal by less than one column's count).  Returns a dict
+    (``positions``: the CSR position of every plan position) or None without hubs."""
+    num_rows = int(indptr.shape[0]) - 1
+    is_hub = (indptr[1:] - indptr[:-1]) >= hub_degree
+    hub_rows = th.nonzero(is_hub).reshape(-1)
+    nh = int(hub_rows.shape[0])
+    if nh == 0:
+        return None
+    rank = th.cumsum(is_hub.long(), 0) - 1          # hub number of a hub row
+    pos_hub = is_hub[rows.long()]
+    hub_pos = th.nonzero(pos_hub).reshape(-1)       # ascending: row-major, original order
+    light_pos = th.nonzero(~pos_hub).reshape(-1)
+    del pos_hub
+    hcols = indices[hub_pos].long()
+    n_he = int(hcols.shape[0])
+    cuts = th.sort(hcols).values[[(k * n_he) // nb for k in range(1, nb)]]
+    block = th.bucketize(hcols, cuts.contiguous(), right=True)  # cuts <= column
+    vrow = block * nh + rank[rows[hub_pos].long()]
+    del hcols, block
+    order = th.argsort(vrow, stable=True)
+    virt = nb * nh
+    positions = th.cat([hub_pos[order], light_pos])
+    plan_rows = th.cat([vrow[order], rows[light_pos].long() + virt])
+    del order, vrow, hub_pos, light_pos
+    out_ptr = th.zeros(virt + num_rows + 1, dtype=th.int64, device=indptr.device)
+    out_ptr[1:] = th.cumsum(th.bincount(plan_rows, minlength=virt + num_rows), 0)
+    return {"num_blocks": nb, "num_hubs": nh, "hub_nnz": n_he, "positions": positions,
+            "rows": plan_rows.to(th.int32), "indices": indices[positions].contiguous(),
+            "indptr": out_ptr.to(th.int32), "hub_rows": hub_rows.to(th.int32),
+            "cuts": cuts}
+
+
 class ImmutableGraphIndex:
     """The kernels' view of a graph on one device: in-CSR + out-CSR."""
 
@@ -176,6 +215,71 @@ class ImmutableGraphIndex:
                     cols.append(out)
                 self._gather_cols = tuple(cols)
         return self._gather_cols
+
+    # Hub plans (DGLMIGraph.{in,out}_hub_plan): the walk of a copy_u sum with the edges of
+    # hub rows (degree >= HUB_DEGREE) sorted by source block, one block per XCD's L2
+    # (build_hub_plan).  Built once per direction on the first launch that
+    # can take it -- the in-CSR's on the first forward, the out-CSR's on the first source
+    # gradient.  DGLMI_HUB_DEGREE overrides the threshold, 0 turns the plans off.
+    # HUB_HOT_DEGREE (DGLMI_HUB_HOT_DEGREE): the cold-mark threshold of the hub part when
+    # the graph has cold hints; None = the hints' own (HOT_DEGREE).  An XCD's L2 sees an
+    # eighth of the table there, so rows re-read far less often are worth keeping: M1 at
+    # HUB_DEGREE 128, threshold 64 / 32 / 16 / 8 / 4 / none cold: 2.88 / 2.75 / 2.66-2.75 /
+    # 2.65 / 2.66 / 2.68 ms against 3.15-3.16 ms without a plan; HUB_DEGREE 64 / 128 /
+    # 256 / 1024 at threshold 64: 2.94 / 2.88 / 2.86 / 2.92 ms (profiles/hub_plan_sweep.json).
+    HUB_DEGREE = 128
+    HUB_BLOCKS = 8
+    HUB_HOT_DEGREE = 8
+    HUB_MIN_TABLE_BYTES = 256 << 20   # below: the Infinity Cache / the column blocks serve
+    HUB_MIN_EDGE_SHARE = 0.25         # hub edges / nnz
+    HUB_MAX_PARTIAL_SHARE = 0.10      # partial rows written + read / rows gathered
+
+    def hub_plan(self, direction, feat_len):
+        """The ``_ffi.HubPlan`` of the in-CSR (``"in"``) or out-CSR (``"out"``) walk for
+        rows of ``feat_len`` floats, or None when a gate says no.  Whether a plan exists
+        does not depend on the cold hints; only its marked column array does."""
+        csr = self.in_csr if direction == "in" else self.out_csr
+        if (csr.bits != 32 or not (32 < feat_len <= 256 and feat_len % 4 == 0)
+                or csr.num_cols * feat_len * 4 < self.HUB_MIN_TABLE_BYTES):
+            return None
+        plans = self.__dict__.setdefault("_hub_plans", {})
+        if direction not in plans:
+            plans[direction] = self._make_hub_plan(direction, csr)
+        return plans[direction]
+
+    def _make_hub_plan(self, direction, csr):
+        deg = int(os.environ.get("DGLMI_HUB_DEGREE", self.HUB_DEGREE))
+        if deg <= 0 or csr.nnz == 0:
+            return None
+        p = build_hub_plan(csr.indptr, csr.indices, csr.rows, deg, self.HUB_BLOCKS)
+        if p is None:
+            return None
+        virt = p["num_blocks"] * p["num_hubs"]
+        if (p["hub_nnz"] < self.HUB_MIN_EDGE_SHARE * csr.nnz
+                or 2 * virt > self.HUB_MAX_PARTIAL_SHARE * csr.nnz
+                or virt + csr.num_rows >= MAX_NODES):
+            return None
+        hints = self.gather_cols()[0 if direction == "in" else 1]
+        marked = None
+        if hints is not None:
+            marked = hints[p["positions"]]
+            hot = os.environ.get("DGLMI_HUB_HOT_DEGREE", self.HUB_HOT_DEGREE)
+            if hot is not None:
+                # the hub part with a threshold of its own: an XCD's L2 now sees an
+                # eighth of the table, so rows re-read less often may be worth keeping
+                h = p["hub_nnz"]
+                cols = p["indices"][:h]
+                count = th.bincount(csr.indices.long(), minlength=csr.num_cols)
+                marked[:h] = th.where(count[cols.long()] < int(hot), cols | (-2 ** 31), cols)
+        c = _ffi.HubPlan()
+        c.num_blocks, c.num_hubs = p["num_blocks"], p["num_hubs"]
+        c.hub_nnz, c.nnz = p["hub_nnz"], csr.nnz
+        keep = (p["rows"], p["indices"], marked, p["indptr"], p["hub_rows"])
+        c.rows, c.indices = keep[0].data_ptr(), keep[1].data_ptr()
+        c.marked = marked.data_ptr() if marked is not None else None
+        c.indptr, c.hub_rows = keep[3].data_ptr(), keep[4].data_ptr()
+        c._keep = keep  # alive as long as the struct
+        return c
 
     @staticmethod
     def _split_by_column(csr, nb):

@@ -109,6 +109,14 @@ def _cgraph(graph, ws, per_edge, feat_len=0):
     return graph.cstruct(ws, coo=per_edge, col_blocks=nb)
 
 
+def _hub_plan(graph, g, direction, feat_len):
+    """Point the call's graph struct at the walk's hub plan (graph_index.hub_plan), built
+    on the first call that can take it."""
+    plan = graph.hub_plan(direction, feat_len) if hasattr(graph, "hub_plan") else None
+    if plan is not None:
+        setattr(g, direction + "_hub_plan", ctypes.addressof(plan))
+
+
 def _feat_len(t):
     n = 1
     for s in t.shape[1:]:
@@ -225,6 +233,9 @@ def copy_reduce(reducer, graph, target, in_data, out_data, in_map=None, out_map=
     ws = _workspace(graph, _feat_len(out_data), out_data.device)
     g = _cgraph(graph, ws, reducer == "none", _feat_len(out_data))
     epi = _epilogue(epilogue, out_data)
+    if (reducer == "sum" and _TARGET_CODE(target) == 0 and epi is None and in_map is None
+            and out_map is None):
+        _hub_plan(graph, g, "in", _feat_len(out_data))
     args = (reducer.encode(), ctypes.byref(g), _TARGET_CODE(target), _arr(in_data, "in_data"),
             _arr(out_data, "out_data"), _map(in_map, "in_mapping"), _map(out_map, "out_mapping"))
     if epi is None:
@@ -241,6 +252,8 @@ def backward_copy_reduce(reducer, graph, target, in_data, out_data, grad_out_dat
                        ("grad_out_data", grad_out_data), ("grad_in_data", grad_in_data)])
     ws = _workspace(graph, _feat_len(grad_in_data), grad_in_data.device)
     g = _cgraph(graph, ws, _TARGET_CODE(target) == 2, _feat_len(grad_in_data))
+    if reducer == "sum" and _TARGET_CODE(target) == 0 and in_map is None and out_map is None:
+        _hub_plan(graph, g, "out", _feat_len(grad_in_data))
     check_call(_ffi.lib().DGLMIKernelBackwardCopyReduce(
         reducer.encode(), ctypes.byref(g), _TARGET_CODE(target), _arr(in_data, "in_data"),
         _arr(out_data, "out_data"), _arr(grad_out_data, "grad_out_data"),

@@ -134,7 +134,35 @@ typedef struct {
    * a per-edge scalar operand is staged with the walk's rows and columns instead of
    * gathered per lane.  0 = read `data`. */
   int32_t eid_identity;
+  /* Optional hub plans (extension): see DGLMIHubPlan.  in_hub_plan re-orders in_csr's
+   * walk, out_hub_plan out_csr's.  Taken by the copy_u sum without mappings or epilogue
+   * on 32-bit graphs, at the row widths that have a cold-hint variant (32 < F <= 256,
+   * F % 4 == 0); every other launch ignores them.  NULL = the plain walk. */
+  const struct DGLMIHubPlan* in_hub_plan;
+  const struct DGLMIHubPlan* out_hub_plan;
 } DGLMIGraph;
+
+/* A copy_u sum walk that shards the gathers of hub rows (rows of large degree) by source
+ * block, so that each of the eight XCDs' L2 caches holds one block of the gathered table
+ * instead of a copy of every block's hottest rows.  The CSR's positions are re-ordered
+ * into one walk over num_blocks * num_hubs virtual rows followed by the CSR's own rows:
+ *  - first the hub rows' positions, sorted by (source block b, hub h), original order kept
+ *    within a pair; their row is the virtual row b * num_hubs + h;
+ *  - then every other row's positions in CSR order, row = num_blocks * num_hubs + CSR row
+ *    (hub rows are empty here).
+ * Source blocks are contiguous column-id ranges.  The kernel reduces virtual rows into a
+ * scratch table and a last kernel sums each hub row's partials in block order. */
+typedef struct DGLMIHubPlan {
+  int32_t num_blocks;      /* source blocks (8: one per XCD) */
+  int64_t num_hubs;
+  int64_t hub_nnz;         /* positions of the virtual rows */
+  int64_t nnz;             /* == the CSR's nnz */
+  const int32_t* rows;     /* nnz, ascending */
+  const int32_t* indices;  /* nnz, the columns in plan order */
+  const int32_t* marked;   /* the same with cold marks in bit 31 ({in,out}_gather_cols), or NULL */
+  const int32_t* indptr;   /* num_blocks * num_hubs + num_rows + 1 */
+  const int32_t* hub_rows; /* num_hubs, the CSR row of every hub, ascending */
+} DGLMIHubPlan;
 
 /* A contiguous row-major fp32 device array (NDArray / DLTensor subset). */
 typedef struct {
