@@ -1945,6 +1945,8 @@ int DGLMIEdgeSoftmaxNodeLogitsBackward(const DGLMIGraph* graph, const DGLMIArray
 
 int DGLMIProjectSupported(int64_t k, int64_t n) { return dglmi::project_supported(k, n) ? 1 : 0; }
 
+int DGLMIProjectInstance(int64_t k, int64_t n) { return dglmi::project_instance(k, n); }
+
 int DGLMIProject(const float* x, int64_t m, int64_t k, const float* w, int64_t w_rows,
                  int64_t w_stride_k, int64_t w_stride_n, int64_t n, const float* bias, float* y, int device,
                  void* stream) {

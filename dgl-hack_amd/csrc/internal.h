@@ -285,6 +285,9 @@ bool softmax_supported(int64_t H);
 // Tall-skinny projection Y = X W (+ bias) on MFMA (kernels_project.hip): X (M, K)
 // row-major, W (K, N) with strides (swk, swn), Y (M, N) row-major.
 bool project_supported(int64_t K, int64_t N);
+// which kernel launch_project takes for (K, N): the k_project_tile / k_project_glds
+// instance (index into kernels_project.hip's table), -2 k_project itself, -1 unsupported
+int project_instance(int64_t K, int64_t N);
 void launch_project(const float* X, int64_t M, int64_t K, const float* W, int64_t swk, int64_t swn,
                     int64_t N, const float* bias, float* Y, hipStream_t s);
 int64_t softmax_chunk_edges(int64_t nnz, int64_t H);

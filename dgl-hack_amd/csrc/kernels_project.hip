@@ -585,15 +585,24 @@ bool force_tile() {
   return e != nullptr && e[0] == '1';
 }
 
+// the shapes k_project takes itself (each wave streams its own X rows)
+bool project_direct(int64_t K, int64_t N) {
+  return (K == 16 || K == 32 || K == 64 || K == 128) && (N == 64 || N == 128) && !force_tile();
+}
+
 }  // namespace
 
 bool project_supported(int64_t K, int64_t N) { return K >= 1 && N >= 1 && N <= (1 << 20) && pick_tile(K, N) >= 0; }
 
+int project_instance(int64_t K, int64_t N) {
+  if (!project_supported(K, N)) return -1;
+  return project_direct(K, N) ? -2 : pick_tile(K, N);
+}
+
 void launch_project(const float* X, int64_t M, int64_t K, const float* W, int64_t swk, int64_t swn,
                     int64_t N, const float* bias, float* Y, hipStream_t s) {
   if (M == 0) return;
-  const bool direct = (K == 16 || K == 32 || K == 64 || K == 128) && (N == 64 || N == 128) && !force_tile();
-  if (direct) {
+  if (project_direct(K, N)) {
     const int64_t slices = N / kNW;
     const int64_t rtiles = (M + 15) / 16;
     // one wave per SIMD over the chip (256 CUs x 4), split between the column slices

@@ -291,6 +291,7 @@ _SIGS = {
         ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array),
         ctypes.POINTER(Array), ctypes.c_float, ctypes.POINTER(Array), ctypes.c_void_p]),
     "DGLMIProjectSupported": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    "DGLMIProjectInstance": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
     "DGLMIProject": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,

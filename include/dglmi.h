@@ -534,8 +534,13 @@ int DGLMIEdgeSoftmaxNodeLogitsBackward(const DGLMIGraph* graph, const DGLMIArray
  * w_stride_k + j * w_stride_n] (a transposed nn.Linear weight is strides (1, k)), bias
  * (n) or NULL, y (m, n) row-major; device pointers on `device`, x / y / bias 16-byte
  * aligned.  w_rows must equal k (a mismatch is an error, as torch.matmul's).
- * DGLMIProjectSupported(k, n): 1 <= k <= 640, 1 <= n <= 2^20 (extension). */
+ * DGLMIProjectSupported(k, n): 1 <= k <= 640, 1 <= n <= 2^20 (extension).
+ * DGLMIProjectInstance(k, n): which kernel DGLMIProject launches for (k, n) under the
+ * current DGLMI_PROJECT_* environment -- the index of the tile instance (0..11, the
+ * table in csrc/kernels_project.hip), -2 the direct kernel (k in {16, 32, 64, 128},
+ * n in {64, 128}), -1 unsupported; no device work (for tests and probes). */
 int DGLMIProjectSupported(int64_t k, int64_t n);
+int DGLMIProjectInstance(int64_t k, int64_t n);
 int DGLMIProject(const float* x, int64_t m, int64_t k, const float* w, int64_t w_rows,
                  int64_t w_stride_k, int64_t w_stride_n, int64_t n, const float* bias, float* y,
                  int device, void* stream);

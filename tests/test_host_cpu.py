@@ -239,6 +239,66 @@ def test_rgcn_fused_ok_matches_the_kernel_rule():
     assert not K.rgcn_fused_ok(32, 64, 1) and not K.rgcn_fused_ok(64, 129, 1)
 
 
+# kernels_project.hip kTileCfgs: (KB, CB, NS) of the k_project_tile / k_project_glds instances
+PROJECT_TILES = [(1, 4, 4), (2, 4, 4), (4, 4, 4), (4, 10, 4), (4, 4, 2), (8, 4, 2), (16, 1, 4),
+                 (8, 4, 1), (40, 1, 4), (4, 4, 1), (10, 4, 1), (4, 5, 4)]
+
+
+def _project_pick(k, n):
+    """kernels_project.hip pick_tile restated: the instance of least padded MFMA work,
+    an extra column slice priced at 10 %, a k split at 5 %, an unsplit K > 256 at 50 %."""
+    best, best_cost = -1, 0.0
+    for i, (kb, cb, ns) in enumerate(PROJECT_TILES):
+        kp, nsl = (4 // ns) * 16 * kb, ns * 16 * cb
+        if k > kp:
+            continue
+        slices = (n + nsl - 1) // nsl
+        cost = (float(kp) * slices * nsl * (1.0 + 0.1 * (slices - 1)) * (1.05 if ns < 4 else 1.0)
+                * (1.5 if ns == 4 and 16 * kb > 256 else 1.0))
+        if best < 0 or cost < best_cost:
+            best, best_cost = i, cost
+    return best
+
+
+def test_project_instance_export(monkeypatch):
+    """DGLMIProjectInstance reports the kernel DGLMIProject launches: pick_tile's choice
+    (restated above) for every K <= 640, -2 where k_project takes the shape itself, -1
+    where there is none; DGLMI_PROJECT_CFG / DGLMI_PROJECT_TILE are read on every call."""
+    L = _ffi.lib()
+    for name in ("DGLMI_PROJECT_CFG", "DGLMI_PROJECT_GLDS", "DGLMI_PROJECT_TILE"):
+        monkeypatch.delenv(name, raising=False)
+    widths = [1, 33, 64, 65, 128, 256, 320, 321, 602, 640, 1000]
+    picked = set()
+    for k in range(1, 641):
+        for n in widths:
+            direct = k in (16, 32, 64, 128) and n in (64, 128)
+            want = -2 if direct else _project_pick(k, n)
+            assert L.DGLMIProjectInstance(k, n) == want, (k, n)
+            picked.add(want)
+    # the cost function never picks these two for K <= 640 at these widths (A/B only)
+    assert picked == {-2} | (set(range(12)) - {8, 9})
+    for k, n in [(641, 64), (0, 64), (64, 0), (64, (1 << 20) + 1)]:
+        assert L.DGLMIProjectInstance(k, n) == -1 and not L.DGLMIProjectSupported(k, n)
+    assert L.DGLMIProjectInstance(640, 1 << 20) >= 0
+    # the tile kernel for the shapes k_project covers
+    monkeypatch.setenv("DGLMI_PROJECT_TILE", "1")
+    for k in (16, 32, 64, 128):
+        for n in (64, 128):
+            assert L.DGLMIProjectInstance(k, n) == _project_pick(k, n) >= 0
+    monkeypatch.delenv("DGLMI_PROJECT_TILE")
+    # a forced instance where K fits it (any N: more column slices), the pick elsewhere
+    for i, (kb, cb, ns) in enumerate(PROJECT_TILES):
+        kp = (4 // ns) * 16 * kb
+        monkeypatch.setenv("DGLMI_PROJECT_CFG", str(i))
+        for n in (1, 65, 1000):
+            assert L.DGLMIProjectInstance(kp, n) == i
+            assert L.DGLMIProjectInstance(kp - 1, n) == i
+            assert L.DGLMIProjectInstance(kp + 1, n) == (_project_pick(kp + 1, n) if kp < 640 else -1)
+        assert L.DGLMIProjectInstance(64, 64) == -2
+    monkeypatch.setenv("DGLMI_PROJECT_CFG", "12")
+    assert L.DGLMIProjectInstance(602, 64) == _project_pick(602, 64) == 10
+
+
 def test_gatconv_fused_route_limits():
     """GATConv takes the fused kernels only where they apply: 32-bit device CSRs, and
     with attention dropout in training gathered tables below 2^31 elements (the

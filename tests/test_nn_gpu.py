@@ -224,9 +224,13 @@ def test_project_tile_kernel(k, n, wt):
     K <= 640 (GATConv's 602 -> 64 on Reddit and its dX 64 -> 602), wide N (R-GCN's
     64 -> 256 with one X read), odd widths (per-element LDS staging of a row span that is
     not float4-aligned; float2 / scalar stores), a row count off the 16-row tile, plain
-    and transposed weights, with and without bias -- against fp64 (every instance of
-    kernels_project.hip's table: 16 / 32 / 64 x 256, 64 x 640, 128 x 128, 256 x 128,
-    256 / 512 / 640 x 64; each in its K % 4 == 0, K even and K odd LDS image)."""
+    and transposed weights, with and without bias -- against fp64.  What the list
+    reaches, by pick_tile: instances 0, 1, 2, 3, 4, 5, 6, 7 and 10 of kernels_project.hip's
+    table (not 8, 9, 11), each in the padded K % 4 == 0 image of k_project_tile; the K odd
+    and K % 4 == 2 cases (instances 0, 1, 2, 6, 10) take the LDS-DMA kernel k_project_glds,
+    and with this odd row count only its 4-byte tail copy.  The register-staged RAW
+    images, the remaining instances, the other row counts and non-finite neighbours are
+    tests/test_project_shapes_gpu.py's."""
     from dgl import kernel as K
     g = th.Generator(device=DEV).manual_seed(3 * k + n)
     m = K.PROJECT_MIN_ROWS + 21
