@@ -836,6 +836,18 @@ int64_t gat_bwd_chunk_edges(int64_t nnz) {
   return k;
 }
 
+// Point a walk at a CSR -- the in- / out-CSR or one of their column blocks -- with the
+// forward's (gat_chunk_edges) or the backward walks' (gat_bwd_chunk_edges) chunk size.
+void gat_set_csr(GatArgs& a, const DGLMICsr& c, int64_t (*chunk_edges)(int64_t)) {
+  a.indptr = c.indptr;
+  a.rows = c.rows;
+  a.indices = c.indices;
+  a.eids = c.data;
+  a.nnz = c.nnz;
+  a.num_rows = c.num_rows;
+  a.chunk = chunk_edges(std::max<int64_t>(c.nnz, 1));
+}
+
 GatArgs gat_args(const DGLMIGraph* g, const DGLMIArray* ft, const DGLMIArray* el,
                  const DGLMIArray* er, float slope, DGLMIArray* out, DGLMIArray* mx,
                  DGLMIArray* sm) {
@@ -861,11 +873,7 @@ GatArgs gat_args(const DGLMIGraph* g, const DGLMIArray* ft, const DGLMIArray* el
   DGLMI_CHECK(aligned16(ft->data) && aligned16(out->data), "feat_src/out must be 16-byte aligned");
   GatArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.indptr = in.indptr;
-  a.rows = in.rows;
-  a.indices = in.indices;
-  a.nnz = in.nnz;
-  a.num_rows = in.num_rows;
+  gat_set_csr(a, in, gat_chunk_edges);
   a.H = static_cast<int>(H);
   a.D = static_cast<int>(D);
   a.F = H * D;
@@ -876,7 +884,6 @@ GatArgs gat_args(const DGLMIGraph* g, const DGLMIArray* ft, const DGLMIArray* el
   a.out = out->data;
   a.m = mx->data;
   a.l = sm->data;
-  a.chunk = gat_chunk_edges(std::max<int64_t>(in.nnz, 1));
   a.o32 = std::max(ft->shape[0], in.num_rows) * a.F < (int64_t(1) << 31);
   return a;
 }
@@ -1039,57 +1046,93 @@ void gat_check_ls(const GatArgs& a, const DGLMIArray* lf, const DGLMIArray* ls) 
   DGLMI_CHECK(aligned16(lf->data), "slope_feat must be 16-byte aligned");
 }
 
-// attention dropout parameters of the GatArgs (p = 0 and no keep words: off).  Hashed
-// mask: 16-bit uniforms per edge and head (internal.h gat_head_keep), p resolved to
-// 2^-16 as t = round(p 2^16); a weight is kept when its uniform is >= t, so the keep
-// probability is (2^16 - t) / 2^16 and the scale its inverse (the rescaled expectation
-// stays unbiased); t = 2^16 (p >= 1 - 2^-17, p = 1 included) keeps nothing, scale 0.
-// Caller's mask (`keep`, one uint32 word per edge id, bit h = head h kept): the kernels
-// read it through the walk's edge ids and scale kept weights by `keep_scale`.
-// torch's own draws (`draw`, DGLMIFusedGatDraw*): the kernels recompute the fused dropout
-// kernel's Philox draw of element e * H + h (internal.h dropout_draw_slot) for edge e.
-void gat_set_draw(GatArgs& a, const DGLMIDropoutDraw* d, int64_t num_edges) {
-  DGLMI_CHECK(d->vec == 1 || d->vec == 2 || d->vec == 4, "dropout draw: vec must be 1, 2 or 4");
-  DGLMI_CHECK(d->threads >= 1, "dropout draw: threads >= 1");
-  DGLMI_CHECK(d->offset % 4 == 0, "dropout draw: the generator offset is a multiple of 4");
-  DGLMI_CHECK((num_edges * a.H) % d->vec == 0, "dropout draw: E x H is not a multiple of vec");
-  DGLMI_CHECK(std::isfinite(d->keep) && d->keep >= 0.0f && d->keep <= 1.0f, "dropout draw: keep in [0, 1]");
-  DGLMI_CHECK(std::isfinite(d->scale) && d->scale >= 0.0f, "dropout draw: scale finite and >= 0");
-  a.drop = 1;
-  a.drop_rng = 1;
-  a.rng_seed = d->seed;
-  a.rng_ctr = d->offset / 4;
-  a.rng_threads = d->threads;
-  a.rng_vec = d->vec;
-  a.rng_shift = (d->threads & (d->threads - 1)) == 0 ? __builtin_ctzll(static_cast<uint64_t>(d->threads)) : -1;
-  a.rng_keep = d->keep;
-  a.drop_scale = d->scale;
+// torch's fused dropout draw as launched (DGLMIDropoutDraw) over `numel` elements
+void check_draw(const DGLMIDropoutDraw& d, int64_t numel) {
+  DGLMI_CHECK(d.vec == 1 || d.vec == 2 || d.vec == 4, "dropout draw: vec must be 1, 2 or 4");
+  DGLMI_CHECK(d.threads >= 1, "dropout draw: threads >= 1");
+  DGLMI_CHECK(d.offset % 4 == 0, "dropout draw: the generator offset is a multiple of 4");
+  DGLMI_CHECK(numel % d.vec == 0, "dropout draw: the element count (E x H) is not a multiple of vec");
+  DGLMI_CHECK(std::isfinite(d.keep) && d.keep >= 0.0f && d.keep <= 1.0f, "dropout draw: keep in [0, 1]");
+  DGLMI_CHECK(std::isfinite(d.scale) && d.scale >= 0.0f, "dropout draw: scale finite and >= 0");
 }
 
-void gat_set_dropout(GatArgs& a, float p, uint64_t seed, const void* keep = nullptr, int keep_bits = 0,
-                     float keep_scale = 0.0f, int64_t num_edges = 0, int keep_pos = 0,
-                     const DGLMIDropoutDraw* draw = nullptr) {
-  if (draw != nullptr) {
-    gat_set_draw(a, draw, num_edges);
-  } else if (keep != nullptr || keep_bits != 0) {
-    a.drop_pos = keep_pos != 0 ? 1 : 0;
-    a.drop_off = 0;
-    DGLMI_CHECK(keep_bits == 8 || keep_bits == 16 || keep_bits == 32, "keep_bits must be 8, 16 or 32");
-    DGLMI_CHECK(a.H <= keep_bits, "keep words narrower than the head count");
-    DGLMI_CHECK(keep != nullptr || num_edges == 0, "keep (one word per edge) is required");
-    DGLMI_CHECK(std::isfinite(keep_scale) && keep_scale >= 0.0f, "keep_scale must be finite and >= 0");
-    a.drop = 2;
-    a.drop_bits = keep;
-    a.drop_width = keep_bits;
-    a.drop_scale = keep_scale;
-  } else {
-    DGLMI_CHECK(p >= 0.0f && p <= 1.0f, "attn_drop must be in [0, 1]");
-    a.drop = p > 0.0f ? 1 : 0;
-    if (!a.drop) return;
-    const double t = std::min(65536.0, std::floor(static_cast<double>(p) * 65536.0 + 0.5));
-    a.drop_thresh = static_cast<uint32_t>(t);
-    a.drop_scale = t < 65536.0 ? static_cast<float>(65536.0 / (65536.0 - t)) : 0.0f;
-    a.drop_seed = seed;
+// log2(threads) when the draw's thread count is a power of two (the capped grid), else -1
+int rng_shift(const DGLMIDropoutDraw& d) {
+  return (d.threads & (d.threads - 1)) == 0 ? __builtin_ctzll(static_cast<uint64_t>(d.threads)) : -1;
+}
+
+// torch's own draws: the kernels recompute the fused dropout kernel's Philox draw of
+// element e * H + h (internal.h dropout_draw_slot) for edge e
+void gat_set_draw(GatArgs& a, const DGLMIDropoutDraw& d, int64_t num_edges) {
+  check_draw(d, num_edges * a.H);
+  a.drop = 1;
+  a.drop_rng = 1;
+  a.rng_seed = d.seed;
+  a.rng_ctr = d.offset / 4;
+  a.rng_threads = d.threads;
+  a.rng_vec = d.vec;
+  a.rng_shift = rng_shift(d);
+  a.rng_keep = d.keep;
+  a.drop_scale = d.scale;
+}
+
+// The attention dropout of one fused GAT call: off, or the form of one exported family
+// (DGLMIFusedGatDropout* / Keep* / Draw*), made by that family's entries and read by
+// gat_set_dropout alone.
+struct GatDropout {
+  enum Kind { OFF, HASHED, KEEP, DRAW } kind = OFF;
+  float p = 0.0f;  // HASHED: the mask a hash of the seed and the edge id
+  uint64_t seed = 0;
+  const void* keep = nullptr;  // KEEP: the caller's mask, one word of keep_bits bits per edge
+  int keep_bits = 0;
+  int keep_by_position = 0;
+  float keep_scale = 0.0f;
+  const DGLMIDropoutDraw* draw = nullptr;  // DRAW: torch's own draws (non-null)
+};
+
+GatDropout gat_hashed_dropout(float p, uint64_t seed) { return {GatDropout::HASHED, p, seed}; }
+GatDropout gat_keep_dropout(const void* keep, int keep_bits, int keep_by_position, float keep_scale) {
+  return {GatDropout::KEEP, 0.0f, 0, keep, keep_bits, keep_by_position, keep_scale};
+}
+GatDropout gat_draw_dropout(const DGLMIDropoutDraw* draw) {
+  return {GatDropout::DRAW, 0.0f, 0, nullptr, 0, 0, 0.0f, draw};
+}
+
+// The attention dropout parameters of the GatArgs.  Hashed mask: 16-bit uniforms per edge
+// and head (internal.h gat_head_keep), p resolved to 2^-16 as t = round(p 2^16); a weight
+// is kept when its uniform is >= t, so the keep probability is (2^16 - t) / 2^16 and the
+// scale its inverse (the rescaled expectation stays unbiased); t = 2^16 (p >= 1 - 2^-17,
+// p = 1 included) keeps nothing, scale 0; p = 0 is off.  Caller's mask (one word per edge,
+// bit h = head h kept): the kernels read it through the walk's edge ids, or at the walk's
+// positions, and scale kept weights by keep_scale.
+void gat_set_dropout(GatArgs& a, const GatDropout& d, int64_t num_edges) {
+  switch (d.kind) {
+    case GatDropout::OFF:
+      return;
+    case GatDropout::HASHED: {
+      DGLMI_CHECK(d.p >= 0.0f && d.p <= 1.0f, "attn_drop must be in [0, 1]");
+      a.drop = d.p > 0.0f ? 1 : 0;
+      if (!a.drop) return;
+      const double t = std::min(65536.0, std::floor(static_cast<double>(d.p) * 65536.0 + 0.5));
+      a.drop_thresh = static_cast<uint32_t>(t);
+      a.drop_scale = t < 65536.0 ? static_cast<float>(65536.0 / (65536.0 - t)) : 0.0f;
+      a.drop_seed = d.seed;
+      break;
+    }
+    case GatDropout::KEEP:
+      DGLMI_CHECK(d.keep_bits == 8 || d.keep_bits == 16 || d.keep_bits == 32, "keep_bits must be 8, 16 or 32");
+      DGLMI_CHECK(a.H <= d.keep_bits, "keep words narrower than the head count");
+      DGLMI_CHECK(d.keep != nullptr || num_edges == 0, "keep (one word per edge) is required");
+      DGLMI_CHECK(std::isfinite(d.keep_scale) && d.keep_scale >= 0.0f, "keep_scale must be finite and >= 0");
+      a.drop = 2;
+      a.drop_bits = d.keep;
+      a.drop_width = d.keep_bits;
+      a.drop_scale = d.keep_scale;
+      a.drop_pos = d.keep_by_position != 0 ? 1 : 0;
+      break;
+    case GatDropout::DRAW:
+      gat_set_draw(a, *d.draw, num_edges);
+      break;
   }
   DGLMI_CHECK(a.o32, "attention dropout needs gathered tables below 2^31 elements");
   DGLMI_CHECK(a.H <= 32, "attention dropout in the fused kernels takes at most 32 heads");
@@ -1098,16 +1141,14 @@ void gat_set_dropout(GatArgs& a, float p, uint64_t seed, const void* keep = null
 int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const DGLMIArray* el,
                      const DGLMIArray* er, float negative_slope, DGLMIArray* out,
                      DGLMIArray* max_out, DGLMIArray* sum_out, DGLMIArray* lf, DGLMIArray* ls,
-                     void* stream, float attn_drop = 0.0f, uint64_t seed = 0,
-                     const void* keep = nullptr, int keep_bits = 0, float keep_scale = 0.0f,
-                     int keep_pos = 0, const DGLMIDropoutDraw* draw = nullptr) {
+                     void* stream, const GatDropout& drop) {
   API_BEGIN();
   check_graph32(graph, "fused GAT");
-  DeviceGuard guard(graph->device);
+  // every argument check is host work: the device is touched after the last of them
   GatArgs a = gat_args(graph, feat_src, el, er, negative_slope, out, max_out, sum_out);
   gat_check_ls(a, lf, ls);
-  gat_set_dropout(a, attn_drop, seed, keep, keep_bits, keep_scale, graph->in_csr.nnz, keep_pos, draw);
-  a.eids = graph->in_csr.data;
+  gat_set_dropout(a, drop, graph->in_csr.nnz);
+  DeviceGuard guard(graph->device);
   a.lf = lf ? lf->data : nullptr;
   a.ls = ls ? ls->data : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1150,14 +1191,9 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
     for (int b = 0; b < nb; ++b) {
       const DGLMICsr& c = graph->in_col_blocks[b];
       GatArgs ab = a;
+      gat_set_csr(ab, c, gat_chunk_edges);  // gat_blocks: every block keeps the graph's rows
       ab.drop_off = keep_off;
       keep_off += c.nnz;
-      ab.indptr = c.indptr;
-      ab.rows = c.rows;
-      ab.indices = c.indices;
-      ab.eids = c.data;
-      ab.nnz = c.nnz;
-      ab.chunk = gat_chunk_edges(std::max<int64_t>(c.nnz, 1));
       ab.out = out_part + b * N * a.F;
       ab.m = m_part + b * N * a.H;
       ab.l = l_part + b * N * a.H;
@@ -1193,7 +1229,7 @@ int DGLMIFusedGatForward(const DGLMIGraph* graph, const DGLMIArray* feat_src, co
                          const DGLMIArray* er, float negative_slope, DGLMIArray* out,
                          DGLMIArray* max_out, DGLMIArray* sum_out, void* stream) {
   return gat_forward_impl(graph, feat_src, el, er, negative_slope, out, max_out, sum_out, nullptr,
-                          nullptr, stream);
+                          nullptr, stream, GatDropout());
 }
 
 int DGLMIFusedGatForwardEx(const DGLMIGraph* graph, const DGLMIArray* feat_src, const DGLMIArray* el,
@@ -1201,7 +1237,7 @@ int DGLMIFusedGatForwardEx(const DGLMIGraph* graph, const DGLMIArray* feat_src, 
                            DGLMIArray* max_out, DGLMIArray* sum_out, DGLMIArray* slope_feat,
                            DGLMIArray* slope_sum, void* stream) {
   return gat_forward_impl(graph, feat_src, el, er, negative_slope, out, max_out, sum_out, slope_feat,
-                          slope_sum, stream);
+                          slope_sum, stream, GatDropout());
 }
 
 }  // extern "C"
@@ -1211,19 +1247,17 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
                       const DGLMIArray* er, float negative_slope, const DGLMIArray* out,
                       const DGLMIArray* max_in, const DGLMIArray* sum_in, const DGLMIArray* lf_in,
                       const DGLMIArray* ls_in, const DGLMIArray* grad_out, DGLMIArray* grad_feat_src,
-                      DGLMIArray* grad_el, DGLMIArray* grad_er, void* stream, float attn_drop = 0.0f,
-                      uint64_t seed = 0, const void* keep = nullptr, int keep_bits = 0,
-                      float keep_scale = 0.0f, int keep_pos = 0, const DGLMIDropoutDraw* draw = nullptr) {
+                      DGLMIArray* grad_el, DGLMIArray* grad_er, void* stream, const GatDropout& drop) {
   API_BEGIN();
   check_graph32(graph, "fused GAT");
-  DeviceGuard guard(graph->device);
+  // every argument check up to here is host work: the device is touched after them
   GatArgs a = gat_args(graph, feat_src, el, er, negative_slope, const_cast<DGLMIArray*>(out),
                        const_cast<DGLMIArray*>(max_in), const_cast<DGLMIArray*>(sum_in));
-  gat_set_dropout(a, attn_drop, seed, keep, keep_bits, keep_scale, graph->in_csr.nnz, keep_pos, draw);
-  // with dropout only the slope-aggregate backward (no destination-side walk) applies
-  // with dropout only the slope-aggregate backward applies -- or, for the recomputed
-  // draws (drop_rng), the destination-side walks too (GATConv's composition keeps no
-  // slope aggregates); never the edge-position path
+  gat_set_dropout(a, drop, graph->in_csr.nnz);
+  DeviceGuard guard(graph->device);
+  // with dropout only the slope-aggregate backward (no destination-side walk) applies --
+  // or, for the recomputed draws (drop_rng), the destination-side walks too (GATConv's
+  // composition keeps no slope aggregates); never the edge-position path
   DGLMI_CHECK(!a.drop || lf_in != nullptr || a.drop_rng,
               "attention dropout needs the forward's slope aggregates (slope_feat / slope_sum)");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1241,6 +1275,7 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
   const DGLMICsr& outc = graph->out_csr;
   check_csr(outc, "out_csr", true);
   DGLMI_CHECK(outc.num_rows == n_src, "out_csr rows != feat_src rows");
+  DGLMI_CHECK(outc.nnz == in.nnz, "out_csr edges != in_csr edges");  // one chunk size, one carry count
   if (in.nnz == 0) {
     launch_fill(grad_feat_src->data, n_src * a.F, 0.0f, s);
     launch_fill(grad_el->data, n_src * a.H, 0.0f, s);
@@ -1290,15 +1325,9 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     int64_t keep_off = 0;  // position-ordered keep words: the out-blocks in order
     auto src_walk = [&](const DGLMICsr& c, bool accumulate) {
       GatArgs b = a;
+      gat_set_csr(b, c, gat_bwd_chunk_edges);
       b.drop_off = keep_off;
       keep_off += c.nnz;
-      b.indptr = c.indptr;
-      b.rows = c.rows;
-      b.indices = c.indices;
-      b.eids = c.data;
-      b.nnz = c.nnz;
-      b.num_rows = c.num_rows;
-      b.chunk = gat_bwd_chunk_edges(std::max<int64_t>(c.nnz, 1));
       b.accumulate = accumulate;
       launch_gat_backward_src(b, s);
     };
@@ -1316,11 +1345,7 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     a.t = static_cast<float*>(tbuf.ptr);
     launch_gat_stats(a, s);
     GatArgs b = a;
-    b.indptr = outc.indptr;
-    b.rows = outc.rows;
-    b.indices = outc.indices;
-    b.nnz = outc.nnz;
-    b.num_rows = outc.num_rows;
+    gat_set_csr(b, outc, gat_bwd_chunk_edges);  // eids: read by the dropout instances only
     launch_gat_backward_src(b, s);
     check_hip(hipGetLastError(), "fused GAT backward (src) launch");
     DGLMIGraph gp = *graph;  // no blocks / hints for the gather-sum
@@ -1337,25 +1362,16 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     // column-blocked: block 0 writes every row's stats and the first gradient
     // terms, later blocks add theirs (block order), first the destination side
     // over the source blocks, then the source side over the destination blocks
-    auto set_walk = [](GatArgs& g, const DGLMICsr& c) {
-      g.indptr = c.indptr;
-      g.rows = c.rows;
-      g.indices = c.indices;
-      g.eids = c.data;
-      g.nnz = c.nnz;
-      g.num_rows = c.num_rows;
-      g.chunk = gat_bwd_chunk_edges(std::max<int64_t>(c.nnz, 1));
-    };
     for (int b = 0; b < nb; ++b) {
       GatArgs ab = a;
-      set_walk(ab, graph->in_col_blocks[b]);
+      gat_set_csr(ab, graph->in_col_blocks[b], gat_bwd_chunk_edges);
       ab.accumulate = b > 0;
       ab.skip_stats = b > 0;
       launch_gat_backward_dst(ab, s);
     }
     for (int b = 0; b < nb; ++b) {
       GatArgs ab = a;
-      set_walk(ab, graph->out_col_blocks[b]);
+      gat_set_csr(ab, graph->out_col_blocks[b], gat_bwd_chunk_edges);
       ab.accumulate = b > 0;
       launch_gat_backward_src(ab, s);
     }
@@ -1363,17 +1379,11 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     return 0;
   }
   // destination side on the in-CSR
-  a.eids = in.data;
   launch_gat_backward_dst(a, s);
   check_hip(hipGetLastError(), "fused GAT backward (dst) launch");
   // source side on the out-CSR
   GatArgs b = a;
-  b.indptr = outc.indptr;
-  b.rows = outc.rows;
-  b.indices = outc.indices;
-  b.eids = outc.data;
-  b.nnz = outc.nnz;
-  b.num_rows = outc.num_rows;
+  gat_set_csr(b, outc, gat_bwd_chunk_edges);
   launch_gat_backward_src(b, s);
   check_hip(hipGetLastError(), "fused GAT backward (src) launch");
   API_END();
@@ -1389,7 +1399,7 @@ int DGLMIFusedGatBackward(const DGLMIGraph* graph, const DGLMIArray* feat_src, c
                           const DGLMIArray* grad_out, DGLMIArray* grad_feat_src,
                           DGLMIArray* grad_el, DGLMIArray* grad_er, void* stream) {
   return gat_backward_impl(graph, feat_src, el, er, negative_slope, out, max_in, sum_in, nullptr,
-                           nullptr, grad_out, grad_feat_src, grad_el, grad_er, stream);
+                           nullptr, grad_out, grad_feat_src, grad_el, grad_er, stream, GatDropout());
 }
 
 int DGLMIFusedGatBackwardEx(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1400,7 +1410,7 @@ int DGLMIFusedGatBackwardEx(const DGLMIGraph* graph, const DGLMIArray* feat_src,
                             DGLMIArray* grad_feat_src, DGLMIArray* grad_el, DGLMIArray* grad_er,
                             void* stream) {
   return gat_backward_impl(graph, feat_src, el, er, negative_slope, out, max_in, sum_in, slope_feat,
-                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream);
+                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream, GatDropout());
 }
 
 int DGLMIFusedGatDropoutForward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1409,7 +1419,7 @@ int DGLMIFusedGatDropoutForward(const DGLMIGraph* graph, const DGLMIArray* feat_
                                 DGLMIArray* sum_out, DGLMIArray* slope_feat, DGLMIArray* slope_sum,
                                 void* stream) {
   return gat_forward_impl(graph, feat_src, el, er, negative_slope, out, max_out, sum_out, slope_feat,
-                          slope_sum, stream, attn_drop, seed);
+                          slope_sum, stream, gat_hashed_dropout(attn_drop, seed));
 }
 
 int DGLMIFusedGatDropoutBackward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1420,8 +1430,8 @@ int DGLMIFusedGatDropoutBackward(const DGLMIGraph* graph, const DGLMIArray* feat
                                  const DGLMIArray* grad_out, DGLMIArray* grad_feat_src,
                                  DGLMIArray* grad_el, DGLMIArray* grad_er, void* stream) {
   return gat_backward_impl(graph, feat_src, el, er, negative_slope, out, max_in, sum_in, slope_feat,
-                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream, attn_drop,
-                           seed);
+                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream,
+                           gat_hashed_dropout(attn_drop, seed));
 }
 
 int DGLMIFusedGatKeepForward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1429,12 +1439,8 @@ int DGLMIFusedGatKeepForward(const DGLMIGraph* graph, const DGLMIArray* feat_src
                              const void* keep, int keep_bits, int keep_by_position, float keep_scale,
                              DGLMIArray* out, DGLMIArray* max_out, DGLMIArray* sum_out,
                              DGLMIArray* slope_feat, DGLMIArray* slope_sum, void* stream) {
-  if (keep_bits == 0) {
-    g_last_error = "keep_bits must be 8, 16 or 32";
-    return -1;
-  }
   return gat_forward_impl(graph, feat_src, el, er, negative_slope, out, max_out, sum_out, slope_feat,
-                          slope_sum, stream, 0.0f, 0, keep, keep_bits, keep_scale, keep_by_position);
+                          slope_sum, stream, gat_keep_dropout(keep, keep_bits, keep_by_position, keep_scale));
 }
 
 int DGLMIFusedGatKeepBackward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1444,13 +1450,9 @@ int DGLMIFusedGatKeepBackward(const DGLMIGraph* graph, const DGLMIArray* feat_sr
                               const DGLMIArray* slope_feat, const DGLMIArray* slope_sum,
                               const DGLMIArray* grad_out, DGLMIArray* grad_feat_src,
                               DGLMIArray* grad_el, DGLMIArray* grad_er, void* stream) {
-  if (keep_bits == 0) {
-    g_last_error = "keep_bits must be 8, 16 or 32";
-    return -1;
-  }
   return gat_backward_impl(graph, feat_src, el, er, negative_slope, out, max_in, sum_in, slope_feat,
-                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream, 0.0f, 0,
-                           keep, keep_bits, keep_scale, keep_by_position);
+                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream,
+                           gat_keep_dropout(keep, keep_bits, keep_by_position, keep_scale));
 }
 
 int DGLMIFusedGatDrawForward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1462,7 +1464,7 @@ int DGLMIFusedGatDrawForward(const DGLMIGraph* graph, const DGLMIArray* feat_src
     return -1;
   }
   return gat_forward_impl(graph, feat_src, el, er, negative_slope, out, max_out, sum_out, slope_feat,
-                          slope_sum, stream, 0.0f, 0, nullptr, 0, 0.0f, 0, draw);
+                          slope_sum, stream, gat_draw_dropout(draw));
 }
 
 int DGLMIFusedGatDrawBackward(const DGLMIGraph* graph, const DGLMIArray* feat_src,
@@ -1477,21 +1479,17 @@ int DGLMIFusedGatDrawBackward(const DGLMIGraph* graph, const DGLMIArray* feat_sr
     return -1;
   }
   return gat_backward_impl(graph, feat_src, el, er, negative_slope, out, max_in, sum_in, slope_feat,
-                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream, 0.0f, 0,
-                           nullptr, 0, 0.0f, 0, draw);
+                           slope_sum, grad_out, grad_feat_src, grad_el, grad_er, stream,
+                           gat_draw_dropout(draw));
 }
 
 int DGLMIDropoutDrawMask(const DGLMIDropoutDraw* draw, int64_t n, uint8_t* mask, void* stream) {
   API_BEGIN();
   DGLMI_CHECK(draw != nullptr, "DGLMIDropoutDrawMask: draw is required");
   DGLMI_CHECK(n >= 0 && (n == 0 || mask != nullptr), "DGLMIDropoutDrawMask: n >= 0, mask");
-  DGLMI_CHECK(draw->vec == 1 || draw->vec == 2 || draw->vec == 4, "DGLMIDropoutDrawMask: vec 1, 2 or 4");
-  DGLMI_CHECK(draw->threads >= 1 && draw->offset % 4 == 0, "DGLMIDropoutDrawMask: threads >= 1, offset % 4 == 0");
-  DGLMI_CHECK(n % draw->vec == 0, "DGLMIDropoutDrawMask: n is not a multiple of vec");
-  const int shift =
-      (draw->threads & (draw->threads - 1)) == 0 ? __builtin_ctzll(static_cast<uint64_t>(draw->threads)) : -1;
-  launch_dropout_draw_mask(draw->seed, draw->offset / 4, draw->threads, draw->vec, shift, draw->keep, n, mask,
-                           static_cast<hipStream_t>(stream));
+  check_draw(*draw, n);
+  launch_dropout_draw_mask(draw->seed, draw->offset / 4, draw->threads, draw->vec, rng_shift(*draw), draw->keep,
+                           n, mask, static_cast<hipStream_t>(stream));
   check_hip(hipGetLastError(), "dropout draw mask launch");
   API_END();
 }
@@ -1507,7 +1505,7 @@ int dropout_draw_scale_impl(const DGLMIDropoutDraw* draw, int heads, const int32
   GatArgs a;
   std::memset(&a, 0, sizeof(a));
   a.H = heads;
-  gat_set_draw(a, draw, n);
+  gat_set_draw(a, *draw, n);
   launch_dropout_draw_scale(a, eids, n, out, apply, static_cast<hipStream_t>(stream));
   check_hip(hipGetLastError(), "dropout draw scale launch");
   API_END();

@@ -482,16 +482,14 @@ class FusedGat(th.autograd.Function):
     (DGLMIFusedGatForwardEx: N x H x D + N x H floats), and the backward is a dense pass
     plus the source-side walk -- no destination-side walk.
     DGLMI_GAT_SLOPES=0 keeps the round-3 backward (destination walk / edge positions).
-    ``attn_drop`` > 0: GATConv's attention dropout (gatconv.py:154) inside the same
-    kernels, the mask a hash of ``seed`` and the edge id, recomputed by the backward
-    (DGLMIFusedGatDropout*; always with the slope aggregates).  ``keep`` (E,) keep
-    words with ``keep_scale`` instead: the caller's mask (DGLMIFusedGatKeep*; GATConv's
-    own nn.Dropout draws).  ``draw`` (dgl.kernel.dropout_draw) instead: torch's own draws
+    ``drop`` (dgl.kernel.GatDropout, or None): GATConv's attention dropout (gatconv.py:154)
+    inside the same kernels, always with the slope aggregates -- a mask hashed from a seed
+    and the edge id and recomputed by the backward (DGLMIFusedGatDropout*), the caller's
+    keep words (DGLMIFusedGatKeep*; GATConv's own nn.Dropout draws), or torch's own draws
     recomputed inside the walks (DGLMIFusedGatDraw*; no mask in memory)."""
 
     @staticmethod
-    def forward(ctx, gidx, feat_src, el, er, slope, attn_drop=0.0, seed=0, keep=None,
-                keep_scale=None, draw=None):
+    def forward(ctx, gidx, feat_src, el, er, slope, drop):
         feat_src, el, er = feat_src.contiguous(), el.contiguous(), er.contiguous()
         n_dst = er.shape[0]
         H, D = feat_src.shape[1], feat_src.shape[2]
@@ -500,29 +498,26 @@ class FusedGat(th.autograd.Function):
         sm = feat_src.new_empty((n_dst, H))
         lf = ls = None
         if any(ctx.needs_input_grad[1:4]) and (
-                attn_drop > 0.0 or keep is not None or draw is not None
-                or os.environ.get("DGLMI_GAT_SLOPES", "1") != "0"):
+                drop is not None or os.environ.get("DGLMI_GAT_SLOPES", "1") != "0"):
             lf = feat_src.new_empty((n_dst, H, D))
             ls = feat_src.new_empty((n_dst, H))
-        keep_in = keep_out = None
-        # the caller's mask per direction: by edge id (the walk reads a random word per
-        # edge) or gathered into the walk's position order first (DGLMIGatKeepGather: the
-        # same random reads in a pass of their own, then coalesced reads in the walk);
-        # DGLMI_GAT_KEEP_ORDER = "<fwd>,<bwd>" with each "eid" or "pos" (A/B)
-        order = os.environ.get("DGLMI_GAT_KEEP_ORDER", GAT_KEEP_ORDER).split(",")
-        pos_in, pos_out = order[0] == "pos", order[-1] == "pos"
-        if keep is not None:
-            keep_in = K.gat_keep_walk_order(gidx, keep, feat_src, "in") if pos_in else keep
-            if lf is not None:
-                keep_out = K.gat_keep_walk_order(gidx, keep, feat_src, "out") if pos_out else keep
-        K.fused_gat_forward(gidx, feat_src, el, er, slope, out, mx, sm, lf, ls,
-                            attn_drop=attn_drop, seed=seed, keep=keep_in, keep_scale=keep_scale,
-                            keep_pos=pos_in, draw=draw)
-        del keep_in
-        ctx.draw = draw
-        ctx.gidx, ctx.slope = gidx, slope
-        ctx.attn_drop, ctx.seed = attn_drop, seed
-        ctx.keep, ctx.keep_scale, ctx.keep_pos = keep_out, keep_scale, pos_out
+        bwd_drop = drop
+        if drop is not None and drop.infix == "Keep":
+            # the caller's mask per direction: by edge id (the walk reads a random word per
+            # edge) or gathered into the walk's position order first (DGLMIGatKeepGather: the
+            # same random reads in a pass of their own, then coalesced reads in the walk);
+            # DGLMI_GAT_KEEP_ORDER = "<fwd>,<bwd>" with each "eid" or "pos" (A/B)
+            order = os.environ.get("DGLMI_GAT_KEEP_ORDER", GAT_KEEP_ORDER).split(",")
+            pos_in, pos_out = order[0] == "pos", order[-1] == "pos"
+            words, scale = drop.words, drop.scale
+
+            def ordered(direction, pos):
+                w = K.gat_keep_walk_order(gidx, words, feat_src, direction) if pos else words
+                return K.GatDropout.keep(w, scale, pos)
+            drop = ordered("in", pos_in)
+            bwd_drop = ordered("out", pos_out) if lf is not None else None
+        K.fused_gat_forward(gidx, feat_src, el, er, slope, out, mx, sm, lf, ls, drop=drop)
+        ctx.gidx, ctx.slope, ctx.drop = gidx, slope, bwd_drop
         ctx.slopes = lf is not None
         if lf is not None:
             ctx.save_for_backward(feat_src, el, er, out, mx, sm, lf, ls)
@@ -540,10 +535,8 @@ class FusedGat(th.autograd.Function):
         g_el = th.empty_like(el)
         g_er = th.empty_like(er)
         K.fused_gat_backward(ctx.gidx, feat_src, el, er, ctx.slope, out, mx, sm, grad_out, g_ft,
-                             g_el, g_er, lf, ls, attn_drop=ctx.attn_drop, seed=ctx.seed,
-                             keep=ctx.keep, keep_scale=ctx.keep_scale,
-                             keep_pos=getattr(ctx, "keep_pos", False), draw=ctx.draw)
-        return None, g_ft, g_el, g_er, None, None, None, None, None, None
+                             g_el, g_er, lf, ls, drop=ctx.drop)
+        return None, g_ft, g_el, g_er, None, None
 
 
 def fused_gat(graph, feat_src, el, er, slope, attn_drop=0.0, seed=None, keep=None,
@@ -551,29 +544,31 @@ def fused_gat(graph, feat_src, el, er, slope, attn_drop=0.0, seed=None, keep=Non
     """backend.py:1235 / tensor.py:415-420: softmax attention + aggregation in one kernel.
 
     ``graph`` is a DGLGraph (or an ImmutableGraphIndex); feat_src (N, H, D), el / er
-    (N, H, 1).  Returns (N, H, D).  Attention dropout, two forms:
+    (N, H, 1).  Returns (N, H, D).  Attention dropout, three forms (the first given wins;
+    one :class:`dgl.kernel.GatDropout` from here on):
 
+    * ``draw`` (:func:`dgl.kernel.dropout_draw`, taken for the (E, H) attention tensor):
+      torch's own draws recomputed inside the kernels -- GATConv's default when
+      :func:`dgl.kernel.dropout_draw_ok`;
     * ``keep`` (E,) keep words in edge-id order (:func:`dgl.kernel.gat_keep_bits` of a
       dropout output (E, H, 1)) with ``keep_scale`` (the dropout's 1 / (1 - p)): the
       caller's mask -- GATConv passes its own ``nn.Dropout``'s draws, the reference's;
     * ``attn_drop`` > 0: a hashed mask keyed by ``seed`` (default: drawn from torch's
       default generator, so ``torch.manual_seed`` reproduces it) -- no (E, H) buffer, not
-      torch's draws;
-    * ``draw`` (:func:`dgl.kernel.dropout_draw`, taken for the (E, H) attention tensor):
-      torch's own draws recomputed inside the kernels -- GATConv's default when
-      :func:`dgl.kernel.dropout_draw_ok`."""
+      torch's draws."""
     gidx = graph if hasattr(graph, "in_csr") else graph._graph.get_immutable_gidx(feat_src.device)
-    attn_drop = float(attn_drop)
+    drop = None
     if draw is not None:
-        return FusedGat.apply(gidx, feat_src, el, er, float(slope), 0.0, 0, None, None, draw)
-    if keep is not None:
+        drop = K.GatDropout.draw(draw)
+    elif keep is not None:
         if keep_scale is None:
             raise DGLError("fused_gat: keep needs keep_scale")
-        return FusedGat.apply(gidx, feat_src, el, er, float(slope), 0.0, 0, keep,
-                              float(keep_scale))
-    if attn_drop > 0.0 and seed is None:
-        seed = int(th.randint(0, 2 ** 62, (1,)).item())
-    return FusedGat.apply(gidx, feat_src, el, er, float(slope), attn_drop, int(seed or 0))
+        drop = K.GatDropout.keep(keep, keep_scale)
+    elif float(attn_drop) > 0.0:
+        if seed is None:
+            seed = int(th.randint(0, 2 ** 62, (1,)).item())
+        drop = K.GatDropout.hashed(attn_drop, seed)
+    return FusedGat.apply(gidx, feat_src, el, er, float(slope), drop)
 
 
 class _AttnLogits(th.autograd.Function):
@@ -642,7 +637,8 @@ class GatComposition(th.autograd.Function):
         rst = ft.new_empty((n_dst,) + tuple(ft.shape[1:]))
         K.binary_op_reduce("sum", "mul", view, SRC, EDGE, ft, a, rst)
         del a
-        ctx.gidx, ctx.slope, ctx.draw = gidx, slope, draw
+        ctx.gidx, ctx.slope = gidx, slope
+        ctx.drop = K.GatDropout.draw(draw) if draw is not None else None
         ctx.save_for_backward(ft, el, er, rst, rmax, rsum)
         return rst
 
@@ -651,7 +647,7 @@ class GatComposition(th.autograd.Function):
         ft, el, er, rst, rmax, rsum = ctx.saved_tensors
         g_ft, g_el, g_er = th.empty_like(ft), th.empty_like(el), th.empty_like(er)
         K.fused_gat_backward(ctx.gidx, ft, el, er, ctx.slope, rst, rmax, rsum, grad.contiguous(),
-                             g_ft, g_el, g_er, draw=ctx.draw)
+                             g_ft, g_el, g_er, drop=ctx.drop)
         return None, None, g_ft, g_el, g_er, None, None
 
 

@@ -527,112 +527,95 @@ def dropout_draw_ok(device):
     return _DRAW_OK[idx]
 
 
+class GatDropout:
+    """The attention dropout of a fused GAT call, one value from the module to the C entry.
+    None means off; the three makers are the three exported families:
+
+    * :meth:`hashed` ``(p, seed)`` -- DGLMIFusedGatDropout*: the mask a hash of ``seed`` and
+      the edge id, rebuilt by the backward from the same seed;
+    * :meth:`keep` ``(words, scale, by_position)`` -- DGLMIFusedGatKeep*: the caller's mask,
+      (E,) keep words (:func:`gat_keep_bits`) by edge id, or with ``by_position`` in the
+      walk's position order (:func:`gat_keep_walk_order`: "in" forward, "out" backward);
+    * :meth:`draw` ``(draw)`` -- DGLMIFusedGatDraw*: torch's own draws
+      (:func:`dropout_draw`) recomputed inside the walks.
+
+    ``infix`` names the entries (DGLMIFusedGat<infix>Forward / Backward) and
+    ``needs_slopes`` says whether the backward needs the forward's slope aggregates: the
+    hashed and keep forms have no destination-side walk; the draw form has both."""
+
+    def __init__(self, infix, needs_slopes, **fields):
+        self.infix, self.needs_slopes = infix, needs_slopes
+        self.__dict__.update(fields)
+
+    @classmethod
+    def hashed(cls, p, seed):
+        return cls("Dropout", True, p=float(p), seed=int(seed))
+
+    @classmethod
+    def keep(cls, words, scale, by_position=False):
+        return cls("Keep", True, words=words, scale=float(scale), by_position=bool(by_position))
+
+    @classmethod
+    def draw(cls, draw):
+        return cls("Draw", False, struct=draw)
+
+    def c_args(self, num_edges):
+        """The entry's arguments between ``negative_slope`` and the outputs."""
+        if self.infix == "Dropout":
+            return [self.p, ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF)]
+        if self.infix == "Keep":
+            kp, kb = _keep_words(self.words, "keep", num_edges)
+            return [kp, kb, int(self.by_position), self.scale]
+        return [ctypes.byref(self.struct)]
+
+
 def fused_gat_forward(graph, feat_src, el, er, slope, out, max_out, sum_out, slope_feat=None,
-                      slope_sum=None, attn_drop=0.0, seed=0, keep=None, keep_scale=None,
-                      keep_pos=False, draw=None):
+                      slope_sum=None, drop=None):
     """_CAPI_DGLFusedGatKernel (binary_reduce.cc:380-396) -> DGLMIFusedGatForward, or
     with ``slope_feat`` (N, H, D) / ``slope_sum`` (N, H) DGLMIFusedGatForwardEx: the
     forward also keeps the attention's slope aggregates, so the backward needs no
-    destination-side walk.  ``attn_drop`` > 0: DGLMIFusedGatDropoutForward (GATConv's
-    attention dropout in the same pass, the mask a hash of ``seed`` and the edge id).
-    ``keep`` (E,) keep words (:func:`gat_keep_bits`) with ``keep_scale``:
-    DGLMIFusedGatKeepForward, the caller's mask -- by edge id, or with ``keep_pos`` in the
-    forward walk's position order (:func:`gat_keep_walk_order` "in").  ``draw``
-    (:func:`dropout_draw`): DGLMIFusedGatDrawForward, torch's own draws recomputed."""
+    destination-side walk.  ``drop`` (:class:`GatDropout`): GATConv's attention dropout in
+    the same pass -> DGLMIFusedGatDropoutForward / KeepForward / DrawForward."""
     _check_ctx(graph, [("feat_src", feat_src), ("el", el), ("er", er), ("out", out)])
     g = graph.cstruct(None, col_blocks=gat_col_blocks(graph, feat_src))
-    if draw is not None:
-        check_call(_ffi.lib().DGLMIFusedGatDrawForward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), ctypes.byref(draw), _arr(out, "out"), _arr(max_out, "max_out"),
-            _arr(sum_out, "sum_out"), _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"),
-            _stream(out)))
-        return out
-    if keep is not None:
-        kp, kb = _keep_words(keep, "keep", graph.in_csr.nnz)
-        check_call(_ffi.lib().DGLMIFusedGatKeepForward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), kp, kb, int(bool(keep_pos)), float(keep_scale), _arr(out, "out"),
-            _arr(max_out, "max_out"), _arr(sum_out, "sum_out"), _arr(slope_feat, "slope_feat"),
-            _arr(slope_sum, "slope_sum"), _stream(out)))
-        return out
-    if attn_drop > 0.0:
-        check_call(_ffi.lib().DGLMIFusedGatDropoutForward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), float(attn_drop), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            _arr(out, "out"), _arr(max_out, "max_out"), _arr(sum_out, "sum_out"),
-            _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"), _stream(out)))
-        return out
-    args = [ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), _arr(out, "out"), _arr(max_out, "max_out"), _arr(sum_out, "sum_out")]
-    if slope_feat is None:
-        check_call(_ffi.lib().DGLMIFusedGatForward(*args, _stream(out)))
+    head = [ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"), float(slope)]
+    tail = [_arr(out, "out"), _arr(max_out, "max_out"), _arr(sum_out, "sum_out")]
+    slopes = [_arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum")]
+    if drop is not None:
+        entry = "DGLMIFusedGat%sForward" % drop.infix
+        head += drop.c_args(graph.in_csr.nnz)
     else:
-        check_call(_ffi.lib().DGLMIFusedGatForwardEx(
-            *args, _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"), _stream(out)))
+        entry = "DGLMIFusedGatForward" if slope_feat is None else "DGLMIFusedGatForwardEx"
+        if slope_feat is None:
+            slopes = []
+    check_call(getattr(_ffi.lib(), entry)(*head, *tail, *slopes, _stream(out)))
     return out
 
 
 def fused_gat_backward(graph, feat_src, el, er, slope, out, max_in, sum_in, grad_out,
-                       grad_feat_src, grad_el, grad_er, slope_feat=None, slope_sum=None,
-                       attn_drop=0.0, seed=0, keep=None, keep_scale=None, keep_pos=False,
-                       draw=None):
+                       grad_feat_src, grad_el, grad_er, slope_feat=None, slope_sum=None, drop=None):
     """_CAPI_DGLKernelBackwardFusedGat (binary_reduce.cc:529-549) -> DGLMIFusedGatBackward
-    (or DGLMIFusedGatBackwardEx with the forward's slope aggregates; with ``attn_drop`` > 0
-    DGLMIFusedGatDropoutBackward, the forward's seed; with ``keep``
-    DGLMIFusedGatKeepBackward, the forward's mask -- by edge id, or with ``keep_pos`` in the
-    backward walk's position order, :func:`gat_keep_walk_order` "out"; with ``draw``
-    DGLMIFusedGatDrawBackward, the forward's draw)."""
+    (or DGLMIFusedGatBackwardEx with the forward's slope aggregates; with ``drop``, the
+    forward's :class:`GatDropout` -- keep words in position order re-pointed at the
+    backward walk's -- DGLMIFusedGatDropoutBackward / KeepBackward / DrawBackward)."""
     _check_ctx(graph, [("feat_src", feat_src), ("grad_out", grad_out)])
-    if draw is not None:  # without slope aggregates: the destination-side walks recompute too
+    if drop is not None and drop.needs_slopes and slope_feat is None:
+        raise DGLError("fused GAT dropout backward needs the forward's slope aggregates")
+    head = [_arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"), float(slope)]
+    tail = [_arr(out, "out"), _arr(max_in, "max_in"), _arr(sum_in, "sum_in")]
+    slopes = [_arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum")]
+    grads = [_arr(grad_out, "grad_out"), _arr(grad_feat_src, "grad_feat_src"), _arr(grad_el, "grad_el"),
+             _arr(grad_er, "grad_er"), _stream(grad_out)]
+    if drop is not None:
+        entry = "DGLMIFusedGat%sBackward" % drop.infix
+        head += drop.c_args(graph.in_csr.nnz)
+    else:
+        entry = "DGLMIFusedGatBackward" if slope_feat is None else "DGLMIFusedGatBackwardEx"
+    if entry == "DGLMIFusedGatBackward":  # the one form that may take the edge-position path
+        g, slopes = _gat_bwd_cgraph(graph, feat_src), []
+    else:
         g = graph.cstruct(None, col_blocks=gat_col_blocks(graph, feat_src, backward=True))
-        check_call(_ffi.lib().DGLMIFusedGatDrawBackward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), ctypes.byref(draw), _arr(out, "out"), _arr(max_in, "max_in"),
-            _arr(sum_in, "sum_in"), _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"),
-            _arr(grad_out, "grad_out"), _arr(grad_feat_src, "grad_feat_src"), _arr(grad_el, "grad_el"),
-            _arr(grad_er, "grad_er"), _stream(grad_out)))
-        return
-    if keep is not None:
-        if slope_feat is None:
-            raise DGLError("fused GAT dropout backward needs the forward's slope aggregates")
-        g = graph.cstruct(None, col_blocks=gat_col_blocks(graph, feat_src, backward=True))
-        kp, kb = _keep_words(keep, "keep", graph.in_csr.nnz)
-        check_call(_ffi.lib().DGLMIFusedGatKeepBackward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), kp, kb, int(bool(keep_pos)), float(keep_scale), _arr(out, "out"),
-            _arr(max_in, "max_in"), _arr(sum_in, "sum_in"), _arr(slope_feat, "slope_feat"),
-            _arr(slope_sum, "slope_sum"), _arr(grad_out, "grad_out"),
-            _arr(grad_feat_src, "grad_feat_src"), _arr(grad_el, "grad_el"),
-            _arr(grad_er, "grad_er"), _stream(grad_out)))
-        return
-    if attn_drop > 0.0:
-        if slope_feat is None:
-            raise DGLError("fused GAT dropout backward needs the forward's slope aggregates")
-        g = graph.cstruct(None, col_blocks=gat_col_blocks(graph, feat_src, backward=True))
-        check_call(_ffi.lib().DGLMIFusedGatDropoutBackward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), float(attn_drop), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            _arr(out, "out"), _arr(max_in, "max_in"), _arr(sum_in, "sum_in"),
-            _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"),
-            _arr(grad_out, "grad_out"), _arr(grad_feat_src, "grad_feat_src"),
-            _arr(grad_el, "grad_el"), _arr(grad_er, "grad_er"), _stream(grad_out)))
-        return
-    if slope_feat is None:
-        g = _gat_bwd_cgraph(graph, feat_src)
-        check_call(_ffi.lib().DGLMIFusedGatBackward(
-            ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"),
-            float(slope), _arr(out, "out"), _arr(max_in, "max_in"), _arr(sum_in, "sum_in"),
-            _arr(grad_out, "grad_out"), _arr(grad_feat_src, "grad_feat_src"),
-            _arr(grad_el, "grad_el"), _arr(grad_er, "grad_er"), _stream(grad_out)))
-        return
-    g = graph.cstruct(None, col_blocks=gat_col_blocks(graph, feat_src, backward=True))
-    check_call(_ffi.lib().DGLMIFusedGatBackwardEx(
-        ctypes.byref(g), _arr(feat_src, "feat_src"), _arr(el, "el"), _arr(er, "er"), float(slope),
-        _arr(out, "out"), _arr(max_in, "max_in"), _arr(sum_in, "sum_in"),
-        _arr(slope_feat, "slope_feat"), _arr(slope_sum, "slope_sum"),
-        _arr(grad_out, "grad_out"), _arr(grad_feat_src, "grad_feat_src"), _arr(grad_el, "grad_el"),
-        _arr(grad_er, "grad_er"), _stream(grad_out)))
+    check_call(getattr(_ffi.lib(), entry)(ctypes.byref(g), *head, *tail, *slopes, *grads))
 
 
 def fused_gat_kernel(graph, feat_src, el, er, s, exp, ret, slope):

@@ -162,30 +162,39 @@ class GATConv(nn.Module):
         gidx = graph._graph.get_immutable_gidx(feat_src.device)
         return gidx.eid_perm and gidx.in_csr.nnz > 0
 
+    def _take_draw(self, device, num_edges):
+        """This call's attention dropout as torch's fused dropout draw over the
+        (E, H, 1) attention in edge-id order, for the kernels to recompute -- taken once
+        per forward: the generator advances as this module's nn.Dropout would
+        (dgl.kernel.dropout_draw) -- or None where that does not apply: no dropout in this
+        call, switched off, p outside (0, 1), more than 32 heads, no edges, or a device or
+        stream on which the draws cannot be reproduced (dgl.kernel.dropout_draw_ok)."""
+        if not (self._attn_drop_active() and MODULE_DRAW_IN_KERNEL):
+            return None
+        p = float(self.attn_drop.p)
+        numel = num_edges * self._num_heads
+        if 0.0 < p < 1.0 and self._num_heads <= 32 and numel > 0 and K.dropout_draw_ok(device):
+            return K.dropout_draw(device, numel, p)
+        return None
+
     def _composed_in_positions(self, graph, feat_src, el, er):
         """u_add_v, LeakyReLU, edge_softmax and u_mul_e_sum -- the reference's
         composition, the same kernels -- on the graph's in-CSR position view
-        (ImmutableGraphIndex.position_view): the same values summed in the same order,
-        bit-identical to the edge-id composition (tests/test_nn_gpu.py)."""
+        (ImmutableGraphIndex.position_view): the same values, and with
+        DGLMI_SOFTMAX_OWNED=0 / DGLMI_SOFTMAX_QUAD=0 at H <= 4 (otherwise the softmax sums a
+        row in another order there) summed in the same order, bit-identical to the edge-id
+        composition (tests/test_nn_gpu.py)."""
         gidx = graph._graph.get_immutable_gidx(feat_src.device)
         view = gidx.position_view("in")
         n_dst, m = view.num_dst, view.number_of_edges()
+        draw = self._take_draw(feat_src.device, m)
         if (FUSED_COMPOSITION_BACKWARD and FUSED_LEAKY and type(self.leaky_relu) is nn.LeakyReLU
-                and B.gat_composition_ok(gidx, feat_src, el, er)):
+                and B.gat_composition_ok(gidx, feat_src, el, er)
+                and (draw is not None or not self._attn_drop_active())):
             # the same forward; the backward as the fused GAT's walks (GatComposition) --
             # with attention dropout when its draws can be recomputed in the walks
-            draw = None
-            if self._attn_drop_active():
-                p = float(self.attn_drop.p)
-                numel = m * self._num_heads
-                if (MODULE_DRAW_IN_KERNEL and 0.0 < p < 1.0 and self._num_heads <= 32 and numel > 0
-                        and K.dropout_draw_ok(feat_src.device)):
-                    draw = K.dropout_draw(feat_src.device, numel, p)
-            if draw is not None:
-                return B.gat_composition(gidx, view, feat_src, el, er, self.leaky_relu.negative_slope,
-                                         draw=draw)
-            if not self._attn_drop_active():
-                return B.gat_composition(gidx, view, feat_src, el, er, self.leaky_relu.negative_slope)
+            kw = {} if draw is None else {"draw": draw}
+            return B.gat_composition(gidx, view, feat_src, el, er, self.leaky_relu.negative_slope, **kw)
         if type(self.leaky_relu) is nn.LeakyReLU and FUSED_LEAKY:
             # u_add_v and the activation inside the softmax's passes: the logits are
             # computed where they are read, never stored (bit-identical to the three steps)
@@ -193,22 +202,17 @@ class GATConv(nn.Module):
         else:
             e = B.binary_reduce("none", "add", view, B.SRC, B.DST, el, er, m)
             a = _edge_softmax_on(view, self.leaky_relu(e), n_dst)
-        if self._attn_drop_active():
+        if draw is not None:
+            # the walk-order scale written directly from the recomputed draws (no ones, no
+            # (E, H) draw, no gather)
+            scale = K.dropout_draw_scale(draw, self._num_heads, gidx.in_csr.data, m, a.device)
+            a = a * scale.view(a.shape)
+        elif self._attn_drop_active():
             # nn.Dropout's draws in edge-id order, as dropout(a) in the edge-id
             # composition: (1 * keep) * scale per edge, gathered into walk order; a times
             # it is dropout's (a * keep) * scale bit for bit, and so is the gradient.
-            # With the draws recomputable (dgl.kernel.dropout_draw_ok) the walk-order
-            # scale is written directly from them (no ones, no (E, H) draw, no gather).
-            numel = m * self._num_heads
-            p = float(self.attn_drop.p)
-            if (MODULE_DRAW_IN_KERNEL and 0.0 < p < 1.0 and self._num_heads <= 32 and numel > 0
-                    and K.dropout_draw_ok(a.device)):
-                scale = K.dropout_draw_scale(K.dropout_draw(a.device, numel, p), self._num_heads,
-                                             gidx.in_csr.data, m, a.device)
-                a = a * scale.view(a.shape)
-            else:
-                scale = self.attn_drop(a.new_ones(a.shape))
-                a = a * K.gather_rows(scale, gidx.in_csr.data)
+            scale = self.attn_drop(a.new_ones(a.shape))
+            a = a * K.gather_rows(scale, gidx.in_csr.data)
         return B.binary_reduce("sum", "mul", view, B.SRC, B.EDGE, feat_src, a, n_dst)
 
     def _fused_dim(self):
@@ -227,27 +231,22 @@ class GATConv(nn.Module):
                 kw = {"attn_drop": p}
             else:
                 # this module's nn.Dropout draws on (E, H, 1) in edge-id order: the RNG
-                # draws of the reference's attn_drop(a) (same shape, same layout), packed
-                # from the dropout's boolean mask to one keep word per edge; kept weights
+                # draws of the reference's attn_drop(a) (same shape, same layout) --
+                # recomputed inside the walks, no mask materialised, or packed from
+                # torch.native_dropout's boolean mask to one keep word per edge; kept weights
                 # take torch's scale float(1 / float(1 - p)) (its fused dropout kernel's)
                 gidx = graph if hasattr(graph, "in_csr") else \
                     graph._graph.get_immutable_gidx(feat_src.device)
-                numel = gidx.in_csr.nnz * self._num_heads
-                if MODULE_DRAW_IN_KERNEL and numel > 0 and K.dropout_draw_ok(feat_src.device):
-                    # the same draws recomputed inside the walks: the generator advances
-                    # as this module's nn.Dropout would, no mask is materialised
-                    kw = {"draw": K.dropout_draw(feat_src.device, numel, p)}
-                    return self._fused_call(graph, feat_src, el, er, d, kw)
-                draw = th.empty((gidx.in_csr.nnz, self._num_heads, 1), device=feat_src.device,
-                                dtype=MODULE_DRAW_DTYPE)
-                _, keep = th.native_dropout(draw, p, True)
-                del draw
-                kw = {"keep": K.gat_keep_bits(keep),
-                      "keep_scale": float(np.float32(1.0 / float(np.float32(1.0 - p))))}
-                del keep
-        return self._fused_call(graph, feat_src, el, er, d, kw)
-
-    def _fused_call(self, graph, feat_src, el, er, d, kw):
+                draw = self._take_draw(feat_src.device, gidx.in_csr.nnz)
+                if draw is not None:
+                    kw = {"draw": draw}
+                else:
+                    _, keep = th.native_dropout(
+                        th.empty((gidx.in_csr.nnz, self._num_heads, 1), device=feat_src.device,
+                                 dtype=MODULE_DRAW_DTYPE), p, True)
+                    kw = {"keep": K.gat_keep_bits(keep),
+                          "keep_scale": float(np.float32(1.0 / float(np.float32(1.0 - p))))}
+                    del keep
         if d == self._out_feats:
             return B.fused_gat(graph, feat_src, el, er, self.negative_slope, **kw)
         ft = th.nn.functional.pad(feat_src, (0, d - self._out_feats))

@@ -430,7 +430,9 @@ int DGLMIFusedGatDrawBackward(const DGLMIGraph* graph, const DGLMIArray* feat_sr
                               void* stream);
 /* mask[i] = 1 if the draw keeps element i, else 0, for i < n (n % vec == 0): the whole
  * mask of the draw above (the fused route's self-check against torch.native_dropout, and
- * the tests).  Extension. */
+ * the tests).  Every entry that takes a draw validates it the same way ("dropout draw:
+ * ..."): vec 1, 2 or 4 dividing the element count, threads >= 1, offset % 4 == 0, keep in
+ * [0, 1] and a finite scale >= 0 -- the last two are refused here too.  Extension. */
 int DGLMIDropoutDrawMask(const DGLMIDropoutDraw* draw, int64_t n, uint8_t* mask, void* stream);
 /* out[p * heads + h] = draw->scale if the draw keeps element eids[p] * heads + h, else 0,
  * for p < n (eids NULL = identity; heads <= 32; n = the draw's E): nn.Dropout's output on

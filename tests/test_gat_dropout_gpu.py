@@ -380,11 +380,96 @@ def test_keep_words_by_edge_id_and_by_position_agree(nb, monkeypatch):
         out, mx, sm = (th.empty(n, H, D, device=DEV), th.empty(n, H, device=DEV),
                        th.empty(n, H, device=DEV))
         lf, ls = th.empty(n, H, D, device=DEV), th.empty(n, H, device=DEV)
-        K.fused_gat_forward(gidx, ft, el, er, 0.2, out, mx, sm, lf, ls, keep=kin, keep_scale=2.0,
-                            keep_pos=pos)
+        K.fused_gat_forward(gidx, ft, el, er, 0.2, out, mx, sm, lf, ls,
+                            drop=K.GatDropout.keep(kin, 2.0, pos))
         gf, gl, gr = th.empty_like(ft), th.empty_like(el), th.empty_like(er)
         K.fused_gat_backward(gidx, ft, el, er, 0.2, out, mx, sm, go, gf, gl, gr, lf, ls,
-                             keep=kout, keep_scale=2.0, keep_pos=pos)
+                             drop=K.GatDropout.keep(kout, 2.0, pos))
         res.append((out, lf, ls, gf, gl, gr))
     for a, b in zip(*res):
         assert th.equal(a, b)
+
+
+def _small(H=3, D=8):
+    """200 nodes, 2,001 edges: E is odd, so with H = 3 E x H is odd and takes a vec-1 draw."""
+    g, n = _graph(200, 2001, 71)
+    gidx = g._graph.get_immutable_gidx(th.device(DEV))
+    gen = th.Generator(device=DEV).manual_seed(6)
+    ft = th.randn(n, H, D, device=DEV, generator=gen)
+    el = th.randn(n, H, 1, device=DEV, generator=gen)
+    er = th.randn(n, H, 1, device=DEV, generator=gen)
+    go = th.randn(n, H, D, device=DEV, generator=gen)
+    state = [th.empty(n, H, D, device=DEV), th.empty(n, H, device=DEV), th.empty(n, H, device=DEV)]
+    slopes = [th.empty(n, H, D, device=DEV), th.empty(n, H, device=DEV)]
+    return g, gidx, (ft, el, er), go, state, slopes
+
+
+def _draw_like(d, **fields):
+    vals = {name: getattr(d, name) for name, _ in d._fields_}
+    vals.update(fields)
+    return type(d)(*(vals[name] for name, _ in d._fields_))
+
+
+def test_malformed_dropout_is_refused():
+    """The C entries refuse, before any launch: a draw that torch's fused dropout cannot
+    have launched (vec not 1 / 2 / 4 or not dividing E x H, no threads, a generator offset
+    off the 4-draw grid, a keep probability above 1), keep words narrower than the head
+    count, and -- here already in dgl.kernel -- a hashed or keep-word backward without the
+    forward's slope aggregates."""
+    from dgl._ffi import DGLError
+    g, gidx, (ft, el, er), go, state, slopes = _small()
+    E, H = gidx.in_csr.nnz, ft.shape[1]
+    assert E == 2001 and (E * H) % 2 == 1
+    good = K.dropout_draw(DEV, E * H, 0.5)
+    assert good.vec == 1
+    bad = [(_draw_like(good, vec=3), "vec"), (_draw_like(good, threads=0), "threads"),
+           (_draw_like(good, offset=good.offset + 2), "offset")]
+    for d, what in bad + [(_draw_like(good, keep=1.5), r"keep in \[0, 1\]"),
+                          (_draw_like(good, vec=2), "not a multiple of vec")]:
+        with pytest.raises(DGLError, match=what):
+            K.fused_gat_forward(gidx, ft, el, er, 0.2, *state, *slopes, drop=K.GatDropout.draw(d))
+    for d, what in bad:
+        with pytest.raises(DGLError, match=what):
+            K.dropout_draw_mask(d, E * H, DEV)
+        with pytest.raises(DGLError, match=what):
+            K.dropout_draw_scale(d, H, gidx.in_csr.data, E, DEV)
+    # uint8 keep words hold 8 heads
+    _, gidx16, (ft16, el16, er16), _, state16, slopes16 = _small(H=16, D=4)
+    words = th.zeros(E, dtype=th.uint8, device=DEV)
+    with pytest.raises(DGLError, match="narrower than the head count"):
+        K.fused_gat_forward(gidx16, ft16, el16, er16, 0.2, *state16, *slopes16,
+                            drop=K.GatDropout.keep(words, 2.0))
+    grads = [th.empty_like(ft), th.empty_like(el), th.empty_like(er)]
+    for drop in (K.GatDropout.hashed(0.5, 3), K.GatDropout.keep(words, 2.0)):
+        with pytest.raises(DGLError, match="needs the forward's slope aggregates"):
+            K.fused_gat_backward(gidx, ft, el, er, 0.2, *state, go, *grads, drop=drop)
+
+
+def test_small_draw_and_keep_order_through_autograd(monkeypatch):
+    """On the small odd graph a well-formed draw runs forward and backward to finite values
+    (with the slope aggregates, and without: the destination-side walks), and through
+    dgl.backend.fused_gat the caller's keep words give the same output and gradients bit
+    for bit whether the forward reads them by edge id or, like the backward, in walk order
+    (DGLMI_GAT_KEEP_ORDER "eid,pos" against the default "pos,pos"): the backward's value
+    is the forward's re-pointed at the out-direction words."""
+    g, gidx, (ft, el, er), go, state, slopes = _small()
+    E, H = gidx.in_csr.nnz, ft.shape[1]
+    drop = K.GatDropout.draw(K.dropout_draw(DEV, E * H, 0.5))
+    K.fused_gat_forward(gidx, ft, el, er, 0.2, *state, *slopes, drop=drop)
+    assert all(bool(th.isfinite(t).all()) for t in state + slopes)
+    assert (state[0] != 0).any()
+    for sl in (slopes, []):
+        grads = [th.empty_like(ft), th.empty_like(el), th.empty_like(er)]
+        K.fused_gat_backward(gidx, ft, el, er, 0.2, *state, go, *grads, *sl, drop=drop)
+        assert all(bool(th.isfinite(t).all()) for t in grads)
+    assert B.GAT_KEEP_ORDER == "pos,pos"
+    keep = K.gat_keep_bits(th.nn.functional.dropout(th.ones(E, H, 1, device=DEV), 0.5, True))
+    res = []
+    for order in ("pos,pos", "eid,pos"):
+        monkeypatch.setenv("DGLMI_GAT_KEEP_ORDER", order)
+        leaves = [t.clone().requires_grad_() for t in (ft, el, er)]
+        out = B.fused_gat(g, *leaves, 0.2, keep=keep, keep_scale=2.0)
+        res.append((out.detach(),) + th.autograd.grad(out, leaves, go))
+    for a, b in zip(*res):
+        assert th.equal(a, b)
+    assert (keep != 7).any()  # some head of some edge was dropped

@@ -334,3 +334,90 @@ def test_gatconv_fused_route_limits():
     conv = FusedGATConv(16, 8, 8, attn_drop=0.5).train()
     assert conv._fused_route(g32, big) and conv._fused_route(gview, 10)
     assert not conv._fused_route(g64, 10)
+
+
+def _fused_gat_entry_calls(g, arrays, keep_bits=32, draw=None):
+    """name -> call of each of the twelve fused GAT entries on graph ``g``: ``arrays`` maps
+    an argument's role to its DGLMIArray ("grad" for every backward-only array); one keep
+    word per edge of ``keep_bits`` bits, ``draw`` a DGLMIDropoutDraw or None (null)."""
+    L = _ffi.lib()
+    G = ctypes.byref(g)
+    A = {k: ctypes.byref(v) for k, v in arrays.items()}
+    head = [G, A["ft"], A["el"], A["er"], 0.2]
+    state = [A["out"], A["mx"], A["sm"]]
+    slopes = [A["lf"], A["ls"]]
+    grads = [A["grad"]] * 4
+    keep = (ctypes.c_uint32 * 1)()
+    D = ctypes.byref(draw) if draw is not None else None
+    mid = {"": [], "Dropout": [0.5, 7], "Keep": [keep, keep_bits, 0, 2.0], "Draw": [D]}
+    calls = {}
+    for infix, m in mid.items():
+        s = slopes if infix else []
+        calls["DGLMIFusedGat%sForward" % infix] = head + m + state + s + [None]
+        calls["DGLMIFusedGat%sBackward" % infix] = head + m + state + s + grads + [None]
+    calls["DGLMIFusedGatForwardEx"] = head + state + slopes + [None]
+    calls["DGLMIFusedGatBackwardEx"] = head + state + slopes + grads + [None]
+    calls["DGLMIFusedGatKernel"] = [G, A["ft"], A["el"], A["er"], A["sm"], A["mx"], A["out"], 0.2, None]
+    calls["DGLMIKernelBackwardFusedGat"] = ([G, A["ft"], A["el"], A["er"], A["sm"], A["mx"], A["out"]]
+                                            + grads + [0.2, None])
+    assert len(calls) == 12
+    return {name: (lambda f=getattr(L, name), a=args: f(*a)) for name, args in calls.items()}
+
+
+def _array(*shape):
+    """A DGLMIArray of ``shape`` with no data (zero rows)."""
+    a = _ffi.Array()
+    a.ndim = len(shape)
+    for i, s in enumerate(shape):
+        a.shape[i] = s
+    return a
+
+
+def test_fused_gat_entries_refuse_without_device():
+    """Every fused GAT entry refuses a 64-bit graph, the Keep entries a keep word width of
+    0 and the Draw entries a null draw -- all before any device work."""
+    g = _ffi.Graph()
+    g.num_bits = 64
+    blank = {k: _ffi.Array() for k in ("ft", "el", "er", "out", "mx", "sm", "lf", "ls", "grad")}
+    for name, call in _fused_gat_entry_calls(g, blank, draw=_ffi.DropoutDraw()).items():
+        assert call() == -1, name
+        assert "fused GAT needs a graph of fewer than 2^31 edges" in _ffi.last_error(), name
+    # a well-formed call on a 32-bit graph without rows: only the dropout value is wrong
+    H, D = 8, 8
+    indptr = (ctypes.c_int32 * 1)()
+    g = _ffi.Graph()
+    g.num_bits = 32
+    g.in_csr.indptr = g.out_csr.indptr = ctypes.addressof(indptr)
+    empty = {"ft": _array(0, H, D), "el": _array(0, H, 1), "er": _array(0, H, 1), "out": _array(0, H, D),
+             "mx": _array(0, H), "sm": _array(0, H), "lf": _array(0, H, D), "ls": _array(0, H),
+             "grad": _array(0, H, D)}
+    calls = _fused_gat_entry_calls(g, empty, keep_bits=0)
+    for name in ("DGLMIFusedGatKeepForward", "DGLMIFusedGatKeepBackward"):
+        assert calls[name]() == -1, name
+        assert "keep_bits must be 8, 16 or 32" in _ffi.last_error(), name
+    for name in ("DGLMIFusedGatDrawForward", "DGLMIFusedGatDrawBackward"):
+        assert calls[name]() == -1, name
+        assert name + ": draw is required" in _ffi.last_error(), name
+
+
+def test_fused_gat_dropout_value():
+    """dgl.kernel.GatDropout: each maker names its entries and says whether its backward
+    needs the forward's slope aggregates; dgl.backend.fused_gat refuses keep words
+    without their scale before any device call."""
+    from types import SimpleNamespace
+    import dgl.backend as B
+    from dgl import kernel as K
+    hashed = K.GatDropout.hashed(0.5, -1)
+    keep = K.GatDropout.keep(th.zeros(3, dtype=th.uint8), 2.0, True)
+    draw = K.GatDropout.draw(_ffi.DropoutDraw())
+    assert [(d.infix, d.needs_slopes) for d in (hashed, keep, draw)] == \
+        [("Dropout", True), ("Keep", True), ("Draw", False)]
+    p, seed = hashed.c_args(3)
+    assert p == 0.5 and seed.value == 2 ** 64 - 1  # the seed's low 64 bits
+    assert len(draw.c_args(3)) == 1
+    with pytest.raises(dgl.DGLError, match="uint8 / int16 / int32 ROCm tensor"):
+        keep.c_args(3)  # keep words live on the device
+    gidx = SimpleNamespace(in_csr=SimpleNamespace(bits=32, nnz=3))
+    ft, el = th.zeros(2, 4, 8), th.zeros(2, 4, 1)
+    with pytest.raises(dgl.DGLError, match="keep needs keep_scale"):
+        B.fused_gat(gidx, ft, el, el, 0.2, keep=th.zeros(3, dtype=th.uint8))
