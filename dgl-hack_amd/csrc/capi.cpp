@@ -427,9 +427,9 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
     a.hub_blocks = plan->num_blocks;
     a.hub_nnz = plan->hub_nnz;
   }
-  Scratch carry(g, fast_workspace_bytes(walk.nnz, F), s);
-  a.carry = static_cast<float*>(carry.ptr);
-  a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(carry.ptr) + fast_carry_bytes(walk.nnz, F));
+  const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, F);
+  Scratch carry(g, lay.bytes, s);
+  lay.point(a, carry.ptr);
   launch_fast_reduce(kind, red, a, s);
   check_hip(hipGetLastError(), "fast reduce launch");
 }
@@ -615,9 +615,9 @@ void forward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const D
       return;
     }
     a.chunk = fast_chunk_edges(walk.nnz, D);
-    Scratch carry(g, fast_workspace_bytes(walk.nnz, D), s);
-    a.carry = static_cast<float*>(carry.ptr);
-    a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(carry.ptr) + fast_carry_bytes(walk.nnz, D));
+    const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, D);
+    Scratch carry(g, lay.bytes, s);
+    lay.point(a, carry.ptr);
     launch_generic_lb(op, red, bc, false, a, s);
     check_hip(hipGetLastError(), "generic lb forward launch");
     if (epi) launch_epilogue(out->data, out_rows, D, epi->row_mul, epi->row_div, epi->bias, epi->addend, s);
@@ -794,9 +794,9 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
       return;
     }
     a.chunk = fast_chunk_edges(walk.nnz, Dg);
-    Scratch carry(g, fast_workspace_bytes(walk.nnz, Dg), s);
-    a.carry = static_cast<float*>(carry.ptr);
-    a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(carry.ptr) + fast_carry_bytes(walk.nnz, Dg));
+    const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, Dg);
+    Scratch carry(g, lay.bytes, s);
+    lay.point(a, carry.ptr);
     launch_generic_lb(op, red, bc, true, a, s);
     check_hip(hipGetLastError(), "generic lb backward launch");
     return;
@@ -1179,8 +1179,8 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
                                             gat_chunk_edges(std::max<int64_t>(c, 1)));
     }
     const int64_t part_bytes = (part_floats * static_cast<int64_t>(sizeof(float)) + 255) & ~int64_t(255);
-    const int64_t carry_bytes = (max_chunks * cw * static_cast<int64_t>(sizeof(float)) + 15) & ~int64_t(15);
-    Scratch ws(graph, part_bytes + carry_bytes + max_chunks * static_cast<int64_t>(sizeof(int32_t)), s);
+    const CarryLayout lay(max_chunks, cw);  // after the partial tables
+    Scratch ws(graph, part_bytes + lay.bytes, s);
     // [out parts][lf parts][m parts][l parts][ls parts]: the float4 arrays first
     float* out_part = static_cast<float*>(ws.ptr);
     float* lf_part = lf ? out_part + nb * N * a.F : nullptr;
@@ -1202,8 +1202,7 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
         ab.ls = ls_part + b * N * a.H;
       }
       ab.raw = 1;
-      ab.carry = reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + part_bytes);
-      ab.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(ws.ptr) + part_bytes + carry_bytes);
+      lay.point(ab, static_cast<char*>(ws.ptr) + part_bytes);
       launch_gat_forward(ab, s);
     }
     launch_gat_merge(out_part, m_part, l_part, nb, N, a.H, a.D, out->data, max_out->data,
@@ -1212,11 +1211,9 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
     check_hip(hipGetLastError(), "fused GAT forward (blocked) launch");
     return 0;
   }
-  const int64_t chunks = (walk.nnz + a.chunk - 1) / a.chunk;
-  const int64_t carry_bytes = (chunks * cw * static_cast<int64_t>(sizeof(float)) + 15) & ~int64_t(15);
-  Scratch carry(graph, carry_bytes + chunks * static_cast<int64_t>(sizeof(int32_t)), s);
-  a.carry = static_cast<float*>(carry.ptr);
-  a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(carry.ptr) + carry_bytes);
+  const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, cw);
+  Scratch carry(graph, lay.bytes, s);
+  lay.point(a, carry.ptr);
   launch_gat_forward(a, s);
   check_hip(hipGetLastError(), "fused GAT forward launch");
   API_END();
@@ -1310,11 +1307,10 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
       chunks = std::max(chunks, (c->nnz + k - 1) / k);
     }
   const int64_t stats_bytes = a.num_rows * a.H * 16;
-  const int64_t carry_bytes = (chunks * (a.F + a.H) * static_cast<int64_t>(sizeof(float)) + 15) & ~int64_t(15);
-  Scratch ws(graph, stats_bytes + carry_bytes + chunks * static_cast<int64_t>(sizeof(int32_t)) + 256, s);
+  const CarryLayout lay(chunks, a.F + a.H);  // after the stats, rounded up to 256 B
+  Scratch ws(graph, stats_bytes + lay.bytes + 256, s);
   a.stats = static_cast<float4*>(ws.ptr);
-  a.carry = reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + ((stats_bytes + 255) & ~int64_t(255)));
-  a.seg_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(a.carry) + carry_bytes);
+  lay.point(a, static_cast<char*>(ws.ptr) + ((stats_bytes + 255) & ~int64_t(255)));
   if (lf_in != nullptr) {
     // the forward kept the slope aggregates: stats and grad_er from one dense pass, then
     // the source-side walk(s) only -- no destination-side walk, no per-edge terms
@@ -1705,11 +1701,12 @@ namespace {
 // carries fit in the same room), then the forward edge pass's packed row statistics
 // (edge-id order: each row's max and sum side by side, one request per edge).
 int64_t round256(int64_t b) { return (b + 255) & ~int64_t(255); }
+struct SoftmaxChunked : CarryLayout {  // the chunked walk (chunks of K positions): records of (m, l)
+  SoftmaxChunked(int64_t nnz, int64_t K, int64_t H) : CarryLayout((nnz + K - 1) / K, 2 * H) {}
+};
 int64_t softmax_carry_bytes(int64_t nnz, int64_t H) {
-  const int64_t K = softmax_chunk_edges(nnz, H);
-  const int64_t chunks = (nnz + K - 1) / K;
-  const int64_t chunked = ((chunks * 2 * H * 4 + 15) & ~int64_t(15)) + chunks * 4;
-  return round256(std::max(chunked, softmax_owned_carry_bytes(nnz, H)));
+  return round256(std::max(SoftmaxChunked(nnz, softmax_chunk_edges(nnz, H), H).bytes,
+                           softmax_owned_carry_bytes(nnz, H)));
 }
 }  // namespace
 
@@ -1729,9 +1726,7 @@ void softmax_layout(dglmi::SoftmaxArgs& a, void* ws, bool own_stats) {
     a.stat0 = reinterpret_cast<float*>(base);
     a.stat1 = a.stat0 + a.num_rows * H;
   }
-  a.carry = reinterpret_cast<float*>(base + round256(2 * a.num_rows * H * 4));
-  a.seg_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(a.carry) +
-                                         ((((a.nnz + a.chunk - 1) / a.chunk) * 2 * H * 4 + 15) & ~int64_t(15)));
+  SoftmaxChunked(a.nnz, a.chunk, H).point(a, base + round256(2 * a.num_rows * H * 4));
   if (a.pack) a.stat_pk = reinterpret_cast<float*>(reinterpret_cast<char*>(a.carry) + softmax_carry_bytes(a.nnz, H));
 }
 

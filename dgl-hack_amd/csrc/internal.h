@@ -148,12 +148,20 @@ __device__ __forceinline__ void fill_empty_rows(IP indptr, int64_t num_rows,
 // association on every run), and no group waits on another.  One group folding
 // 39 K carries made a 20 M-edge star's copy_u sum 5.4 ms (0.8 ms spread over
 // 1 M rows; scripts/hub_probe.py).  Counters live after the carries in the
-// workspace, one per chunk, zeroed by the reduce kernel that precedes the fixup.
-// Like fill_empty_rows, seg_arrive_last needs the L lanes of a group inside ONE
-// wavefront (L <= 64: lane 0's counter value reaches the others by a shuffle);
-// the templated kernels static_assert it and the generic ones cap L at 64
-// (kernels_generic.hip kMaxLaneBits).
+// workspace (CarryLayout below), one per chunk, zeroed by the reduce kernel that
+// precedes the fixup (seg_reset).  Like fill_empty_rows, seg_arrive_last needs
+// the L lanes of a group inside ONE wavefront (L <= 64: lane 0's counter value
+// reaches the others by a shuffle; L == 1, one lane per chunk, has no cross-lane
+// operation); the templated kernels static_assert it and the generic ones cap L
+// at 64 (kernels_generic.hip kMaxLaneBits).
+//
+// The protocol is written once, here; every fixup kernel (k_chunk_fixup,
+// k_lane_fixup, k_lb_fixup, k_gat_fwd_fixup, k_gat_bwd_fixup, k_sm_fixup) calls
+// fixup_role for its group's part and seg_fold with its own record handling.
 constexpr int64_t kFixSeg = 32;
+__device__ __forceinline__ void seg_reset(int32_t* seg_cnt, int64_t chunk, int lane) {
+  if (seg_cnt != nullptr && lane == 0) seg_cnt[chunk] = 0;
+}
 __device__ __forceinline__ bool seg_arrive_last(int32_t* cnt, int64_t nseg, int L, int lane) {
   __threadfence();  // release: this group's partial, past its XCD's L2
   int old = 0;
@@ -163,6 +171,66 @@ __device__ __forceinline__ bool seg_arrive_last(int32_t* cnt, int64_t nseg, int 
   if (last) __threadfence();  // acquire: the other segments' partials
   return last;
 }
+
+// What the group of `chunk` does in a fixup: nothing (work false), or row r, whose
+// continuation chunks are first..last.  nseg == 1 (always, without counters): the
+// group of `first` folds them all.  Else the group of every kFixSeg-th one folds
+// chunk..cend.  `a`: the walk's arguments (rows, nnz, chunk, seg_cnt).
+struct FixupRole {
+  bool work;
+  int64_t r, chunk, first, last, nseg, cend;
+};
+template <typename Args, typename IP>
+__device__ __forceinline__ FixupRole fixup_role(const Args& a, IP indptr, int64_t chunk) {
+  FixupRole w{};
+  w.chunk = chunk;
+  const int64_t K = a.chunk;
+  const int64_t p0 = chunk * K;
+  if (chunk == 0 || p0 >= a.nnz) return w;
+  w.r = a.rows[p0];
+  const int64_t start = indptr[w.r];
+  if (start >= p0) return w;  // not a continuation
+  w.first = start / K + 1;    // the row's first continuation chunk
+  w.last = (indptr[w.r + 1] - 1) / K;
+  w.nseg = a.seg_cnt != nullptr ? (w.last - w.first + kFixSeg) / kFixSeg : 1;
+  if (w.nseg == 1 ? chunk != w.first : (chunk - w.first) % kFixSeg != 0) return w;
+  w.cend = w.nseg == 1 ? w.last : (chunk + kFixSeg - 1 < w.last ? chunk + kFixSeg - 1 : w.last);
+  w.work = true;
+  return w;
+}
+
+// The two phases.  fold(false, c0, c1, 1): fold carry records c0..c1 in chunk order
+// and store the partial in record c0.  fold(true, c0, c1, step): fold the row head and
+// records c0, c0 + step, .. c1 in that order and store the finished row.  Whether a
+// segment starts from its own record or from the identity, how many records are
+// loaded ahead and what a record is stay with the kernel (the results depend on the
+// first for -0.0 and NaN).
+template <typename Fold>
+__device__ __forceinline__ void seg_fold(const FixupRole& w, int32_t* seg_cnt, int L, int lane,
+                                         Fold&& fold) {
+  if (w.nseg > 1) {
+    fold(false, w.chunk, w.cend, int64_t(1));
+    if (!seg_arrive_last(seg_cnt + w.first, w.nseg, L, lane)) return;
+    fold(true, w.first, w.first + (w.nseg - 1) * kFixSeg, kFixSeg);
+  } else {
+    fold(true, w.first, w.last, int64_t(1));
+  }
+}
+
+// Host side: where a chunked walk's carries and counters lie in its workspace.
+// `chunks` records of `rec_floats` floats, rounded up to 16 B, then one int32
+// counter per chunk; point() sets a.carry / a.seg_cnt for a workspace at `base`.
+struct CarryLayout {
+  int64_t carry_bytes, bytes;
+  CarryLayout(int64_t chunks, int64_t rec_floats)
+      : carry_bytes((chunks * rec_floats * static_cast<int64_t>(sizeof(float)) + 15) & ~int64_t(15)),
+        bytes(carry_bytes + chunks * static_cast<int64_t>(sizeof(int32_t))) {}
+  template <typename Args>
+  void point(Args& a, void* base) const {
+    a.carry = static_cast<float*>(base);
+    a.seg_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(base) + carry_bytes);
+  }
+};
 
 // binary_reduce_common.h:131-213
 template <int OP>
@@ -350,8 +418,7 @@ struct FastArgs {
   int64_t plan_wgs;     // workgroups remapped to their XCD's source block (a multiple of 8)
 };
 int64_t fast_chunk_edges(int64_t nnz, int64_t F);
-int64_t fast_workspace_bytes(int64_t nnz, int64_t F);  // carries + counters
-int64_t fast_carry_bytes(int64_t nnz, int64_t F);      // offset of the counters
+int64_t fast_workspace_bytes(int64_t nnz, int64_t F);  // carries + counters (CarryLayout)
 // Returns false if the shape is not supported by the fast path.
 bool fast_supported(int kind, int64_t F, int64_t head_dim);
 void launch_fast_reduce(int kind, int red, const FastArgs& a, hipStream_t s);  // needs a.indptr

@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd(GatArgs a) {
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // the fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   const int F4 = static_cast<int>(a.F / 4);
   const int H = a.H, D = a.D;
   const int64_t CW = LS ? 2 * a.F + 3 * H : a.F + 2 * H;  // carry record, see above
@@ -413,21 +413,9 @@ template <int L, int NV, bool LS>
 __global__ void __launch_bounds__(kBlock) k_gat_fwd_fixup(GatArgs a) {
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront");
   constexpr int G = kBlock / L;
-  const int g = threadIdx.x / L;
   const int lane = threadIdx.x % L;
-  const int64_t chunk = (int64_t)blockIdx.x * G + g;
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = a.indptr[r];
-  if (start >= p0) return;  // not a continuation
-  // segmented for long rows (internal.h, kFixSeg)
-  const int64_t first = start / K + 1;
-  const int64_t last = (a.indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
-  const int64_t cend = nseg == 1 ? last : (chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last);
+  const FixupRole w = fixup_role(a, a.indptr, (int64_t)blockIdx.x * G + threadIdx.x / L);
+  if (!w.work) return;
   const int F4 = static_cast<int>(a.F / 4);
   const int H = a.H;
   const int64_t CW = LS ? 2 * a.F + 3 * H : a.F + 2 * H;
@@ -451,50 +439,43 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd_fixup(GatArgs a) {
     }
     mx = mn;
   };
-  if (nseg > 1) {
+  // a record is (acc, m, l) (+ the slope aggregates (lf, ls)): one carry record, or the
+  // row's entries of out / m / l (/ lf / ls).  A segment starts from its own record;
+  // only the finished row is normalised (unless a.raw).
+  seg_fold(w, a.seg_cnt, L, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* cr = a.carry + c0 * CW;
+    float* pa = head ? a.out + w.r * a.F : cr;
+    float* pm = head ? a.m + w.r * H : cr + a.F;
+    float* pl = head ? a.l + w.r * H : cr + a.F + H;
+    float* pq = head ? a.lf + w.r * a.F : cr + a.F + 2 * H;
+    float* ps = head ? a.ls + w.r * H : cr + 2 * a.F + 2 * H;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int f4 = lane + v * L;
       if (f4 >= F4) continue;
       const int h = (4 * f4) / a.D;
-      float* cr = a.carry + chunk * CW;
-      float4 acc = ld4g(cr + 4 * f4);
-      float mx = cr[a.F + h], sm = cr[a.F + H + h];
-      float4 qa = LS ? ld4g(cr + a.F + 2 * H + 4 * f4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      float qs = LS ? cr[2 * a.F + 2 * H + h] : 0.0f;
-      for (int64_t c = chunk + 1; c <= cend; ++c) merge(acc, mx, sm, qa, qs, c, f4, h);
-      st4g(cr + 4 * f4, acc);
-      if (LS) st4g(cr + a.F + 2 * H + 4 * f4, qa);
+      float4 acc = ld4g(pa + 4 * f4);
+      float mx = pm[h], sm = pl[h];
+      float4 qa = LS ? ld4g(pq + 4 * f4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float qs = LS ? ps[h] : 0.0f;
+      for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) merge(acc, mx, sm, qa, qs, c, f4, h);
+      if (head) {
+        const float inv = a.raw ? 1.0f : (sm > 0.0f ? 1.0f / sm : 0.0f);
+        acc = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
+        if (LS) {
+          qa = make_float4(qa.x * inv, qa.y * inv, qa.z * inv, qa.w * inv);
+          qs = qs * inv;
+        }
+      }
+      st4g(pa + 4 * f4, acc);
+      if (LS) st4g(pq + 4 * f4, qa);
       if ((4 * f4) % a.D == 0) {
-        cr[a.F + h] = mx;
-        cr[a.F + H + h] = sm;
-        if (LS) cr[2 * a.F + 2 * H + h] = qs;
+        pm[h] = mx;
+        pl[h] = sm;
+        if (LS) ps[h] = qs;
       }
     }
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, L, lane)) return;
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int f4 = lane + v * L;
-    if (f4 >= F4) continue;
-    const int h = (4 * f4) / a.D;
-    float4 acc = ld4g(a.out + r * a.F + 4 * f4);
-    float mx = a.m[r * H + h], sm = a.l[r * H + h];
-    float4 qa = LS ? ld4g(a.lf + r * a.F + 4 * f4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float qs = LS ? a.ls[r * H + h] : 0.0f;
-    if (nseg > 1)
-      for (int64_t sg = 0; sg < nseg; ++sg) merge(acc, mx, sm, qa, qs, first + sg * kFixSeg, f4, h);
-    else
-      for (int64_t c = first; c <= last; ++c) merge(acc, mx, sm, qa, qs, c, f4, h);
-    const float inv = a.raw ? 1.0f : (sm > 0.0f ? 1.0f / sm : 0.0f);
-    st4g(a.out + r * a.F + 4 * f4, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
-    if (LS) st4g(a.lf + r * a.F + 4 * f4, make_float4(qa.x * inv, qa.y * inv, qa.z * inv, qa.w * inv));
-    if ((4 * f4) % a.D == 0) {
-      a.m[r * H + h] = mx;
-      a.l[r * H + h] = sm;
-      if (LS) a.ls[r * H + h] = qs * inv;
-    }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -520,7 +501,7 @@ __global__ void __launch_bounds__(kBlock) k_gat_bwd_dst(GatArgs a) {
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // the fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   const int F4 = static_cast<int>(a.F / 4);
   const int H = a.H, D = a.D, D4 = a.D / 4;
   int hd[NV], fl[NV];
@@ -656,7 +637,7 @@ __device__ __forceinline__ void gat_bwd_src_body(const GatArgs& a) {
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // the fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   const int F4 = static_cast<int>(a.F / 4);
   const int H = a.H, D = a.D, D4 = a.D / 4;
   const int64_t CW = a.F + H;
@@ -833,65 +814,37 @@ __global__ void __launch_bounds__(kBlock) k_gat_bwd_fixup(GatArgs a, float* vec_
                                                           int with_vec) {
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront");
   constexpr int G = kBlock / L;
-  const int g = threadIdx.x / L;
   const int lane = threadIdx.x % L;
-  const int64_t chunk = (int64_t)blockIdx.x * G + g;
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = a.indptr[r];
-  if (start >= p0) return;  // not a continuation
-  // segmented for long rows (internal.h, kFixSeg)
-  const int64_t first = start / K + 1;
-  const int64_t last = (a.indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
-  const int64_t cend = nseg == 1 ? last : (chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last);
+  const FixupRole w = fixup_role(a, a.indptr, (int64_t)blockIdx.x * G + threadIdx.x / L);
+  if (!w.work) return;
   const int F4 = static_cast<int>(a.F / 4);
   const int H = a.H;
   const int64_t CW = with_vec ? a.F + H : H;
   const int64_t hoff = with_vec ? a.F : 0;
-  const float4 Z = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto add = [&](float4& accf, float& acce, int64_t c, int f4, int h, bool lead) {
-    const float* cr = a.carry + c * CW;
-    if (with_vec) {
-      const float4 t = ld4g(cr + 4 * f4);
-      accf = make_float4(accf.x + t.x, accf.y + t.y, accf.z + t.z, accf.w + t.w);
-    }
-    if (lead) acce += cr[hoff + h];
-  };
-  if (nseg > 1) {
+  // a segment starts from zero, the finished row from its entries of vec_out / head_out
+  seg_fold(w, a.seg_cnt, L, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* pv = head ? vec_out + w.r * a.F : a.carry + c0 * CW;
+    float* ph = head ? head_out + w.r * H : a.carry + c0 * CW + hoff;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int f4 = lane + v * L;
       if (f4 >= F4) continue;
       const int h = (4 * f4) / a.D;
       const bool lead = (4 * f4) % a.D == 0;
-      float4 accf = Z;
-      float acce = 0.0f;
-      for (int64_t c = chunk; c <= cend; ++c) add(accf, acce, c, f4, h, lead);
-      float* cr = a.carry + chunk * CW;
-      if (with_vec) st4g(cr + 4 * f4, accf);
-      if (lead) cr[hoff + h] = acce;
+      float4 accf = head && with_vec ? ld4g(pv + 4 * f4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float acce = head && lead ? ph[h] : 0.0f;
+      for (int64_t c = c0; c <= c1; c += step) {
+        const float* cr = a.carry + c * CW;
+        if (with_vec) {
+          const float4 t = ld4g(cr + 4 * f4);
+          accf = make_float4(accf.x + t.x, accf.y + t.y, accf.z + t.z, accf.w + t.w);
+        }
+        if (lead) acce += cr[hoff + h];
+      }
+      if (with_vec) st4g(pv + 4 * f4, accf);
+      if (lead) ph[h] = acce;
     }
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, L, lane)) return;
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int f4 = lane + v * L;
-    if (f4 >= F4) continue;
-    const int h = (4 * f4) / a.D;
-    const bool lead = (4 * f4) % a.D == 0;
-    float4 accf = with_vec ? ld4g(vec_out + r * a.F + 4 * f4) : Z;
-    float acce = lead ? head_out[r * H + h] : 0.0f;
-    if (nseg > 1)
-      for (int64_t sg = 0; sg < nseg; ++sg) add(accf, acce, first + sg * kFixSeg, f4, h, lead);
-    else
-      for (int64_t c = first; c <= last; ++c) add(accf, acce, c, f4, h, lead);
-    if (with_vec) st4g(vec_out + r * a.F + 4 * f4, accf);
-    if (lead) head_out[r * H + h] = acce;
-  }
+  });
 }
 
 // Merge the unnormalised per-block softmax partials of a column-blocked forward

@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(kBlock) k_lb_reduce(EdgeArgs a, int lane_bits)
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // k_lb_fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   const int64_t Do = BWD ? a.D * a.len : a.D;
   const int nv = static_cast<int>((Do + L - 1) / L);
   const float I = BWD ? 0.0f : red_identity<RED>();
@@ -239,38 +239,19 @@ __global__ void __launch_bounds__(kBlock) k_lb_fixup(EdgeArgs a, int lane_bits) 
   const int L = 1 << lane_bits;
   const int G = kBlock >> lane_bits;
   const int lane = threadIdx.x & (L - 1);
-  const int64_t chunk = (int64_t)blockIdx.x * G + (threadIdx.x >> lane_bits);
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = a.indptr[r];
-  if (start >= p0) return;  // not a continuation
-  // segmented for long rows (internal.h, kFixSeg)
-  const int64_t first = start / K + 1;
-  const int64_t last = (a.indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
+  const FixupRole w = fixup_role(a, a.indptr, (int64_t)blockIdx.x * G + (threadIdx.x >> lane_bits));
+  if (!w.work) return;
   const int64_t Do = BWD ? a.D * a.len : a.D;
-  auto red = [&](float acc, float t) { return BWD ? acc + t : red_apply<RED>(acc, t); };
-  if (nseg > 1) {
-    const int64_t cend = chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last;
+  // a segment starts from its own record
+  seg_fold(w, a.seg_cnt, L, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* dst = head ? a.out + lb_out_row<BWD>(a, w.r) * Do : a.carry + c0 * Do;
     for (int64_t k = lane; k < Do; k += L) {
-      float acc = a.carry[chunk * Do + k];
-      for (int64_t c = chunk + 1; c <= cend; ++c) acc = red(acc, a.carry[c * Do + k]);
-      a.carry[chunk * Do + k] = acc;
+      float acc = dst[k];
+      for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step)
+        acc = BWD ? acc + a.carry[c * Do + k] : red_apply<RED>(acc, a.carry[c * Do + k]);
+      dst[k] = acc;
     }
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, L, lane)) return;
-  }
-  float* o = a.out + lb_out_row<BWD>(a, r) * Do;
-  for (int64_t k = lane; k < Do; k += L) {
-    float acc = o[k];
-    if (nseg > 1)
-      for (int64_t sg = 0; sg < nseg; ++sg) acc = red(acc, a.carry[(first + sg * kFixSeg) * Do + k]);
-    else
-      for (int64_t c = first; c <= last; ++c) acc = red(acc, a.carry[c * Do + k]);
-    o[k] = acc;
-  }
+  });
 }
 
 __global__ void k_fill(float* __restrict__ out, int64_t n, float v) {

@@ -100,48 +100,31 @@ __device__ __forceinline__ void merge1(float& m, float& l, float m2, float l2) {
 
 template <int H, int MODE>
 __global__ void __launch_bounds__(kBlock) k_sm_fixup(SoftmaxArgs a) {
-  const int64_t chunk = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = a.indptr[r];
-  if (start >= p0) return;  // not a continuation
-  // segmented for long rows (internal.h, kFixSeg); one lane per chunk
-  const int64_t first = start / K + 1;
-  const int64_t last = (a.indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
-  float m[H], l[H];
-  auto add = [&](int64_t c) {
-    float cm[H], cl[H];
-    ldrow<H>(a.carry + c * 2 * H, cm);
-    if constexpr (MODE == SM_STATS) {
-      ldrow<H>(a.carry + c * 2 * H + H, cl);
+  // one lane per chunk
+  const FixupRole w = fixup_role(a, a.indptr, (int64_t)blockIdx.x * kBlock + threadIdx.x);
+  if (!w.work) return;
+  // a record is (m, l) (SM_STATS) or one sum; a segment starts from its own record
+  seg_fold(w, a.seg_cnt, 1, 0, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* dm = head ? a.stat0 + w.r * H : a.carry + c0 * 2 * H;
+    float* dl = head ? a.stat1 + w.r * H : a.carry + c0 * 2 * H + H;
+    float m[H], l[H];
+    ldrow<H>(dm, m);
+    if constexpr (MODE == SM_STATS) ldrow<H>(dl, l);
+    for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) {
+      float cm[H], cl[H];
+      ldrow<H>(a.carry + c * 2 * H, cm);
+      if constexpr (MODE == SM_STATS) {
+        ldrow<H>(a.carry + c * 2 * H + H, cl);
 #pragma unroll
-      for (int h = 0; h < H; ++h) merge(m[h], l[h], cm[h], cl[h]);
-    } else {
+        for (int h = 0; h < H; ++h) merge(m[h], l[h], cm[h], cl[h]);
+      } else {
 #pragma unroll
-      for (int h = 0; h < H; ++h) m[h] += cm[h];
+        for (int h = 0; h < H; ++h) m[h] += cm[h];
+      }
     }
-  };
-  if (nseg > 1) {
-    const int64_t cend = chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last;
-    ldrow<H>(a.carry + chunk * 2 * H, m);
-    if constexpr (MODE == SM_STATS) ldrow<H>(a.carry + chunk * 2 * H + H, l);
-    for (int64_t c = chunk + 1; c <= cend; ++c) add(c);
-    strow<H>(a.carry + chunk * 2 * H, m);
-    if constexpr (MODE == SM_STATS) strow<H>(a.carry + chunk * 2 * H + H, l);
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, 1, 0)) return;
-  }
-  ldrow<H>(a.stat0 + r * H, m);
-  if constexpr (MODE == SM_STATS) ldrow<H>(a.stat1 + r * H, l);
-  if (nseg > 1)
-    for (int64_t sg = 0; sg < nseg; ++sg) add(first + sg * kFixSeg);
-  else
-    for (int64_t c = first; c <= last; ++c) add(c);
-  strow<H>(a.stat0 + r * H, m);
-  if constexpr (MODE == SM_STATS) strow<H>(a.stat1 + r * H, l);
+    strow<H>(dm, m);
+    if constexpr (MODE == SM_STATS) strow<H>(dl, l);
+  });
 }
 
 // One lane per edge; items in edge-id order (coo_dst) or in-CSR order.  (Two or four
@@ -1388,7 +1371,7 @@ __global__ void __launch_bounds__(kBlock) k_sm_rows_v(SoftmaxArgs a) {
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // k_sm_fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   OwnedWalk<H, MODE, true> walk(a, lane);
   const int first_row = a.rows[p0];
   if (p0 > 0 && a.rows[p0 - 1] == first_row) {

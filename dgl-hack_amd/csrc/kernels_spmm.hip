@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(kBlock) k_lane_reduce(FastArgs a) {
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr) a.seg_cnt[chunk] = 0;  // k_lane_fixup's counters
+  seg_reset(a.seg_cnt, chunk, 0);
   const float I = red_identity<RED>();
   float ident[F];
 #pragma unroll
@@ -208,41 +208,24 @@ __global__ void __launch_bounds__(kBlock) k_lane_reduce(FastArgs a) {
 
 template <int RED, int F, bool EPI = false>
 __global__ void __launch_bounds__(kBlock) k_lane_fixup(FastArgs a) {
-  const int64_t chunk = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = a.indptr[r];
-  if (start >= p0) return;  // not a continuation
-  // segmented for long rows (internal.h, kFixSeg); one lane per chunk
-  const int64_t first = start / K + 1;
-  const int64_t last = (a.indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
-  float acc[F];
-  auto add = [&](int64_t c) {
-    float t[F];
-    load_row<F>(a.carry + c * F, t);
+  // one lane per chunk
+  const FixupRole w = fixup_role(a, a.indptr, (int64_t)blockIdx.x * kBlock + threadIdx.x);
+  if (!w.work) return;
+  // a segment starts from its own record
+  seg_fold(w, a.seg_cnt, 1, 0, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* dst = head ? a.out + w.r * F : a.carry + c0 * F;
+    float acc[F];
+    load_row<F>(dst, acc);
+    for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) {
+      float t[F];
+      load_row<F>(a.carry + c * F, t);
 #pragma unroll
-    for (int i = 0; i < F; ++i) acc[i] = red_apply<RED>(acc[i], t[i]);
-  };
-  if (nseg > 1) {
-    const int64_t cend = chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last;
-    load_row<F>(a.carry + chunk * F, acc);
-    for (int64_t c = chunk + 1; c <= cend; ++c) add(c);
-    store_row<F>(a.carry + chunk * F, acc);
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, 1, 0)) return;
-  }
-  load_row<F>(a.out + r * F, acc);
-  if (nseg > 1)
-    for (int64_t sg = 0; sg < nseg; ++sg) add(first + sg * kFixSeg);
-  else
-    for (int64_t c = first; c <= last; ++c) add(c);
-  epi_row<EPI, F>(a, r, acc);
-  store_row<F>(a.out + r * F, acc);
+      for (int i = 0; i < F; ++i) acc[i] = red_apply<RED>(acc[i], t[i]);
+    }
+    if (head) epi_row<EPI, F>(a, w.r, acc);
+    store_row<F>(dst, acc);
+  });
 }
-
 
 template <int KIND, int RED, int F>
 void run_lane(const FastArgs& a, hipStream_t s) {
@@ -336,17 +319,11 @@ int64_t fast_chunk_edges(int64_t nnz, int64_t F) {
   return k;
 }
 
-int64_t fast_carry_bytes(int64_t nnz, int64_t F) {
-  if (nnz == 0) return 0;
-  const int64_t k = fast_chunk_edges(nnz, F);
-  return (((nnz + k - 1) / k) * F * static_cast<int64_t>(sizeof(float)) + 15) & ~int64_t(15);
-}
-
 // carries + one segmented-fixup counter per chunk
 int64_t fast_workspace_bytes(int64_t nnz, int64_t F) {
   if (nnz == 0) return 0;
   const int64_t k = fast_chunk_edges(nnz, F);
-  return fast_carry_bytes(nnz, F) + ((nnz + k - 1) / k) * static_cast<int64_t>(sizeof(int32_t));
+  return CarryLayout((nnz + k - 1) / k, F).bytes;
 }
 
 bool fast_supported(int kind, int64_t F, int64_t head_dim) {

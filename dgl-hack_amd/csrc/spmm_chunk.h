@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
   const int64_t p0 = chunk * K;
   if (p0 >= a.nnz) return;  // whole group exits together
   const int64_t p1 = p0 + K < a.nnz ? p0 + K : a.nnz;
-  if (a.seg_cnt != nullptr && lane == 0) a.seg_cnt[chunk] = 0;  // k_chunk_fixup's counters
+  seg_reset(a.seg_cnt, chunk, lane);
   using V = typename VecT<VW>::T;
   const int F4 = static_cast<int>(a.F / VW);
   const V I = vident<VW, RED>();
@@ -445,28 +445,25 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
 // chunk order.  One group per chunk; a row's first continuation chunk does the
 // work, or -- for rows of more than kFixSeg continuation chunks, when the
 // workspace has counters -- every kFixSeg-th one folds a segment and the last
-// to finish folds the head and the segment partials (internal.h).
+// to finish folds the head and the segment partials (internal.h, seg_fold).
 template <int RED, int L, int NV, bool EPI = false, int VW = 4, bool PLAN = false>
 __global__ void __launch_bounds__(kBlock) k_chunk_fixup(FastArgs a, IdxPtr indptr) {
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront (seg_arrive_last)");
   constexpr int G = kBlock / L;
-  const int g = threadIdx.x / L;
   const int lane = threadIdx.x % L;
-  const int64_t chunk = (int64_t)blockIdx.x * G + g;
-  const int64_t K = a.chunk;
-  const int64_t p0 = chunk * K;
-  if (chunk == 0 || p0 >= a.nnz) return;
-  const int64_t r = a.rows[p0];
-  const int64_t start = indptr[r];
-  if (start >= p0) return;  // not a continuation
-  const int64_t first = start / K + 1;  // the row's first continuation chunk
-  const int64_t last = (indptr[r + 1] - 1) / K;
-  const int64_t nseg = a.seg_cnt != nullptr ? (last - first + kFixSeg) / kFixSeg : 1;
-  if (nseg == 1 ? chunk != first : (chunk - first) % kFixSeg != 0) return;
-  const int64_t cend = nseg == 1 ? last : (chunk + kFixSeg - 1 < last ? chunk + kFixSeg - 1 : last);
+  const FixupRole w = fixup_role(a, indptr, (int64_t)blockIdx.x * G + threadIdx.x / L);
+  if (!w.work) return;
   using V = typename VecT<VW>::T;
   const int F4 = static_cast<int>(a.F / VW);
-  auto fold = [&](V (&acc)[NV], int64_t c0, int64_t c1, int64_t step) {
+  // a segment starts from the identity; four carries are loaded ahead of their folds
+  seg_fold(w, a.seg_cnt, L, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* dst = head ? row_dst<PLAN>(a, w.r) : a.carry + c0 * a.F;
+    V acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int f4 = lane + v * L;
+      acc[v] = head && f4 < F4 ? vld<VW>(dst + VW * f4) : vident<VW, RED>();
+    }
     int64_t c = c0;
     for (; c + 3 * step <= c1; c += 4 * step) {
       V t[4][NV];
@@ -488,32 +485,12 @@ __global__ void __launch_bounds__(kBlock) k_chunk_fixup(FastArgs a, IdxPtr indpt
         const int f4 = lane + v * L;
         if (f4 < F4) acc[v] = vred<RED>(acc[v], vld<VW>(a.carry + c * a.F + VW * f4));
       }
-  };
-  V acc[NV];
-  if (nseg > 1) {
-    // this segment's partial, into its own first carry record (already read)
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = vident<VW, RED>();
-    fold(acc, chunk, cend, 1);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int f4 = lane + v * L;
-      if (f4 < F4) vst(a.carry + chunk * a.F + VW * f4, acc[v]);
+      if (f4 < F4) vst(dst + VW * f4, head ? epiv<EPI, VW>(a, acc[v], w.r, f4) : acc[v]);
     }
-    if (!seg_arrive_last(a.seg_cnt + first, nseg, L, lane)) return;
-  }
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int f4 = lane + v * L;
-    acc[v] = f4 < F4 ? vld<VW>(row_dst<PLAN>(a, r) + VW * f4) : vident<VW, RED>();
-  }
-  if (nseg > 1) fold(acc, first, first + (nseg - 1) * kFixSeg, kFixSeg);
-  else fold(acc, first, last, 1);
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int f4 = lane + v * L;
-    if (f4 < F4) vst(row_dst<PLAN>(a, r) + VW * f4, epiv<EPI, VW>(a, acc[v], r, f4));
-  }
+  });
 }
 
 // The hub plan's last step (after the fixup, whose name it carries: the benchmark's

@@ -421,3 +421,25 @@ def test_fused_gat_dropout_value():
     ft, el = th.zeros(2, 4, 8), th.zeros(2, 4, 1)
     with pytest.raises(dgl.DGLError, match="keep needs keep_scale"):
         B.fused_gat(gidx, ft, el, el, 0.2, keep=th.zeros(3, dtype=th.uint8))
+
+
+def test_workspace_bytes_match_recorded_layout():
+    """DGLMIKernelWorkspaceBytes / DGLMIEdgeSoftmaxWorkspaceBytes over edge counts around
+    the chunk sizes and past 2^31, every row-slot width and every softmax head count:
+    callers may pass their own workspace, so the sizes (carries rounded up to 16 B, one
+    counter per chunk; csrc/internal.h CarryLayout) stay what they were when
+    tests/golden/workspace_bytes.json was recorded (from the build before CarryLayout)."""
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")))
+    L = _ffi.lib()
+
+    def csr(rows, nnz):
+        return ctypes.byref(_ffi.CSR(rows, rows, nnz, None, None, None, None))
+
+    nnzs = {1, 7, 8, 9, 4095, 4096, 4097, 10 ** 6, 10 ** 8, 3 * 10 ** 9}
+    assert {e[0] for e in want["kernel"]} == nnzs and {e[1] for e in want["kernel"]} == {1, 6, 15, 16, 64, 602}
+    assert {e[0] for e in want["softmax"]} == nnzs and {e[2] for e in want["softmax"]} == {1, 2, 4, 8, 16}
+    assert len(want["kernel"]) == 60 and len(want["softmax"]) == 100
+    for nnz, f, nbytes in want["kernel"]:
+        assert L.DGLMIKernelWorkspaceBytes(csr(1000, nnz), f) == nbytes, (nnz, f)
+    for nnz, rows, h, nbytes in want["softmax"]:
+        assert L.DGLMIEdgeSoftmaxWorkspaceBytes(csr(rows, nnz), h) == nbytes, (nnz, rows, h)
