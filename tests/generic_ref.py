@@ -17,6 +17,10 @@ Three versions of every per-edge value:
   every subtraction by an addition.  An fp32 evaluation with k roundings is within
   k * 2^-24 * majorant of the fp64 value (to first order), whatever the order of a sum.
 
+For the per-edge kernels (csrc/kernels_sddmm.hip) two more fp32 restatements: the group
+kernel's dot in its own order (``dot_group32``) and the per-edge gradients
+(``edge_grads32``).
+
 Gradients come in the shape the kernel writes (the full broadcast shape, dot length
 included) and, like ``dgl.backend._reduce_grad``, summed down to the operand's shape.
 """
@@ -84,6 +88,65 @@ class EdgeTerms:
         else:
             raise ValueError(op)
         assert self.e32.dtype == np.float32 and self.e32.shape == (m,) + out
+
+
+def dot_group32(L, R):
+    """The dot of k_sddmm_group (csrc/kernels_sddmm.hip) in its own order, fp32 with every
+    operation rounded, for L, R of shape (m, D, len), len % 4 == 0 and S = len / 4 a power of
+    two: the products; per float4 ((x + y) + z) + w; a balanced pairwise tree over
+    min(S, 64) adjacent float4, adjacent pairs first (what the xor butterfly leaves in the
+    lowest lane of a segment); for S > 64, acc = 0; acc = acc + part[v] over the S / 64 slots
+    in order.  Returns (m, D)."""
+    L, R = np.asarray(L, np.float32), np.asarray(R, np.float32)
+    m, D, ln = L.shape
+    S = ln // 4
+    assert L.shape == R.shape and ln % 4 == 0 and S > 0 and S & (S - 1) == 0
+    p = (L * R).reshape(m, D, S, 4)
+    part = ((p[..., 0] + p[..., 1]) + p[..., 2]) + p[..., 3]
+    span = min(S, 64)
+    part = part.reshape(m, D, S // span, span)
+    while part.shape[-1] > 1:
+        part = part[..., 0::2] + part[..., 1::2]
+    part = part[..., 0]
+    if S <= 64:
+        out = part[..., 0]
+    else:
+        out = np.zeros((m, D), np.float32)
+        for v in range(S // span):
+            out = out + part[..., v]
+    assert out.dtype == np.float32
+    return out
+
+
+def edge_grads32(op, L, R, ge):
+    """The per-edge gradients (gl, gr) in fp32 as the per-edge kernels compute them (bwd1 of
+    kernels_sddmm.hip with op_grad_lhs / op_grad_rhs of internal.h), each operation rounded in
+    this order: add ge, ge; sub ge, ge * -1; mul and dot ge * r, ge * l; div ge * (1 / r),
+    ge * (-l / (r * r)); use_lhs ge, None.  L, R (m,) + full (R ignored for use_lhs), ge
+    (m,) + out: for dot the length dim is missing and ge is repeated over it."""
+    L = np.asarray(L, np.float32)
+    ge = np.asarray(ge, np.float32)
+    if op == "dot":
+        ge = np.broadcast_to(ge.reshape(L.shape[:-1])[..., None], L.shape)
+    else:
+        ge = ge.reshape(L.shape)
+    if op == "use_lhs":
+        return ge.copy(), None
+    R = np.asarray(R, np.float32)
+    assert L.shape == R.shape
+    one = np.float32(1)
+    if op == "add":
+        gl, gr = ge * one, ge * one
+    elif op == "sub":
+        gl, gr = ge * one, ge * -one
+    elif op in ("mul", "dot"):
+        gl, gr = ge * R, ge * L
+    elif op == "div":
+        gl, gr = ge * (one / R), ge * (-L / (R * R))
+    else:
+        raise ValueError(op)
+    assert gl.dtype == np.float32 and gr.dtype == np.float32
+    return gl, gr
 
 
 def _flat(a):

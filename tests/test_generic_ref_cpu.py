@@ -181,3 +181,59 @@ def test_feature_shapes_and_reduce_to():
     r, k = R.reduce_to(a, (8,))
     assert k == 20 and r.shape == (2, 8) and np.array_equal(r, a.sum((1, 2)))
     assert R.reduce_to(a, (4, 5, 8))[1] == 1
+
+
+# every dot shape of the per-edge kernels' table (tests/test_sddmm_shapes_gpu.py) that the
+# group kernel's order applies to: len % 4 == 0 and len / 4 a power of two
+GROUP_DOTS = [(1, 4), (2, 4), (1, 8), (3, 4), (1, 16), (5, 4), (4, 8), (9, 4), (2, 32), (17, 4),
+              (1, 128), (33, 4), (1, 256), (65, 4), (2, 256), (1, 512), (129, 4), (3, 256),
+              (2, 512), (1, 1024)]
+
+
+def _dot_operands(shape, rows=1501):
+    rs = np.random.RandomState(shape[0] * 4099 + shape[1])
+    return (rs.uniform(-1, 1, (rows,) + shape).astype(np.float32),
+            rs.uniform(-1, 1, (rows,) + shape).astype(np.float32))
+
+
+@pytest.mark.parametrize("shape", GROUP_DOTS, ids=lambda s: "%dx%d" % s)
+def test_dot_group32(shape):
+    """The group kernel's summation order: within (len + 1) 2^-24 majorant of fp64 (len
+    products and len - 1 additions in any order, the additions of partial sums no larger than
+    the majorant; one more for the fold from 0), the sequential chain itself at len = 4, and
+    a different rounding from the chain in more than a quarter of the elements from len = 32
+    -- so that nobody "simplifies" it to the sequential order."""
+    L, Rr = _dot_operands(shape)
+    t = R.EdgeTerms("dot", L, Rr)
+    got = R.dot_group32(L, Rr)
+    assert got.shape == t.e32.shape and got.dtype == np.float32
+    R.assert_within(got, t.e64, (shape[1] + 1) * R.EPS * t.emaj, "dot_group32 %s" % (shape,))
+    if shape[1] == 4:
+        assert np.array_equal(got, t.e32)
+    if shape[1] >= 32:
+        assert (got != t.e32).mean() > 0.25, (got != t.e32).mean()
+
+
+@pytest.mark.parametrize("op", ["add", "sub", "mul", "div", "dot", "use_lhs"])
+def test_edge_grads32_within_bound_of_fp64(op):
+    """The fp32 restatement of the per-edge gradients against edge_grads' fp64 values, at
+    the bound the GPU tests use for per-edge gradients without a dot chain."""
+    rs = np.random.RandomState(17)
+    shape = (5, 8) if op == "dot" else (40,)
+    L = rs.uniform(-1, 1, (997,) + shape).astype(np.float32)
+    Rr = rs.uniform(-1, 1, (997,) + shape)
+    if op == "div":
+        Rr = (np.abs(Rr) + 0.5) * np.where(Rr < 0, -1.0, 1.0)
+    Rr = Rr.astype(np.float32)
+    t = R.EdgeTerms(op, L, L if op == "use_lhs" else Rr)
+    go = rs.uniform(-1, 1, (997,) + t.out).astype(np.float32)
+    gl, glmaj, gr, grmaj = R.edge_grads("none", t, go)
+    gl32, gr32 = R.edge_grads32(op, L, Rr, go)
+    assert gl32.shape == gl.shape
+    R.assert_within(gl32, gl, R.edge_bound(glmaj, 0), op + " grad lhs")
+    if op == "use_lhs":
+        assert gr32 is None and np.array_equal(gl32, go)
+    else:
+        R.assert_within(gr32, gr, R.edge_bound(grmaj, 0), op + " grad rhs")
+    if op in ("add", "sub"):
+        assert np.array_equal(gl32, go) and np.array_equal(gr32, go if op == "add" else -go)
