@@ -266,14 +266,23 @@ void keep_pool_memory() {
   done[dev] = true;
 }
 
+// Where a Scratch may live: the caller's DGLMIGraph.workspace, or nowhere but the pool
+// (a buffer that must not alias what another Scratch of the call keeps there).
+struct Workspace {
+  void* ptr;
+  int64_t bytes;
+};
+Workspace caller_workspace(const DGLMIGraph* g) { return {g->workspace, g->workspace_bytes}; }
+Workspace no_workspace() { return {nullptr, 0}; }
+
 struct Scratch {
   void* ptr = nullptr;
   bool owned = false;
   hipStream_t s = nullptr;
-  Scratch(const DGLMIGraph* g, int64_t bytes, hipStream_t stream) : s(stream) {
+  Scratch(Workspace ws, int64_t bytes, hipStream_t stream) : s(stream) {
     if (bytes <= 0) return;
-    if (g->workspace != nullptr && g->workspace_bytes >= bytes) {
-      ptr = g->workspace;
+    if (ws.ptr != nullptr && ws.bytes >= bytes) {
+      ptr = ws.ptr;
     } else {
       keep_pool_memory();
       check_hip(hipMallocAsync(&ptr, static_cast<size_t>(bytes), stream), "hipMallocAsync");
@@ -285,12 +294,52 @@ struct Scratch {
   }
 };
 
-// Run a reduce-to-row on the load-balanced kernels.  `walk` is the CSR whose
-// rows own the output; out has `walk.num_rows` rows of F floats.
-void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, const float* x,
-              const int32_t* x_map, const float* w, const int32_t* w_map, float* out, int64_t F,
-              int64_t head_dim, hipStream_t s, const DGLMIEpilogue* epi = nullptr,
-              const float* xr = nullptr);
+// The walk of a reduce-to-row: the CSR whose rows own the output, and every hint that
+// belongs to that CSR.  Made by graph_walk / bare_walk alone, so which walk gets which
+// hint is decided there, by name, and nowhere else.
+struct ReduceWalk {
+  DGLMICsr csr;                // by value: the arrays stay the caller's
+  int wide;                    // indptr and data hold int64 (IdxPtr.wide)
+  bool eid_positions;          // edge p's operand sits at p: csr.data is not read
+  const DGLMICsr* blocks;      // column blocks of csr, num_blocks of them (NULL: none)
+  int num_blocks;
+  const int32_t* marked;       // csr.indices with the cold-column marks (NULL: none)
+  const DGLMIHubPlan* plan;    // NULL: none
+  Workspace ws;                // for the carries
+
+  IdxPtr idx(const int32_t* p) const { return IdxPtr{p, wide}; }
+};
+
+// The graph's own in-CSR (walk_in) or out-CSR with the hints the graph carries for it:
+// a position view's walk (DGLMIGraph.eid_identity bit 1 / 2), or a walk whose edge ids
+// are its positions (data NULL): edge p's operand sits at p
+ReduceWalk graph_walk(const DGLMIGraph* g, bool walk_in) {
+  const DGLMICsr& c = walk_in ? g->in_csr : g->out_csr;
+  return {c,
+          wide(g),
+          (g->eid_identity & (walk_in ? 1 : 2)) != 0 || c.data == nullptr,
+          walk_in ? g->in_col_blocks : g->out_col_blocks,
+          g->num_col_blocks,
+          walk_in ? g->in_gather_cols : g->out_gather_cols,
+          walk_in ? g->in_hub_plan : g->out_hub_plan,
+          caller_workspace(g)};
+}
+
+// Any other CSR over g's nodes (a column block, a relation-expanded or re-addressed
+// walk): no blocks, marks or plan, and its own `data` says whether edge ids are
+// positions (NULL: the R-GCN state's position-ordered walks).
+ReduceWalk bare_walk(int wide, Workspace ws, const DGLMICsr& c) {
+  return {c, wide, c.data == nullptr, nullptr, 0, nullptr, nullptr, ws};
+}
+ReduceWalk bare_walk(const DGLMIGraph* g, const DGLMICsr& c) {
+  return bare_walk(wide(g), caller_workspace(g), c);
+}
+
+// Run a reduce-to-row on the load-balanced kernels; out has `rw.csr.num_rows` rows of
+// F floats.
+void run_fast(const ReduceWalk& rw, int kind, int red, const float* x, const int32_t* x_map,
+              const float* w, const int32_t* w_map, float* out, int64_t F, int64_t head_dim,
+              hipStream_t s, const DGLMIEpilogue* epi = nullptr, const float* xr = nullptr);
 
 // Column blocks (DGLMIGraph.num_col_blocks) on the load-balanced sum: one pass
 // per non-empty block, so a pass gathers from a slice of the table that fits the
@@ -299,27 +348,24 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
 // Every pass applies row_mul / row_div to its own sum (sum_b acc_b * m / d ==
 // (sum_b acc_b) * m / d up to rounding); the caller's addend enters with the
 // first pass, the bias with the last.  Block order is fixed: deterministic.
-void run_fast_blocked(const DGLMIGraph* g, const DGLMICsr* blocks, const DGLMICsr& walk, int kind,
-                      const float* x, const float* w, const int32_t* w_map, float* out, int64_t F,
-                      int64_t head_dim, hipStream_t s, const DGLMIEpilogue* epi) {
+void run_fast_blocked(const ReduceWalk& rw, int kind, const float* x, const float* w,
+                      const int32_t* w_map, float* out, int64_t F, int64_t head_dim, hipStream_t s,
+                      const DGLMIEpilogue* epi) {
+  const DGLMICsr& walk = rw.csr;
   std::vector<int> nz;
-  for (int b = 0; b < g->num_col_blocks; ++b) {
-    DGLMI_CHECK(blocks[b].num_rows == walk.num_rows && blocks[b].indptr != nullptr,
+  for (int b = 0; b < rw.num_blocks; ++b) {
+    DGLMI_CHECK(rw.blocks[b].num_rows == walk.num_rows && rw.blocks[b].indptr != nullptr,
                 "column blocks must keep the graph's rows");
-    if (blocks[b].nnz > 0) nz.push_back(b);
+    if (rw.blocks[b].nnz > 0) nz.push_back(b);
   }
-  DGLMIGraph plain = *g;  // no blocks / hints for the per-block passes
-  plain.num_col_blocks = 0;
-  plain.in_col_blocks = plain.out_col_blocks = nullptr;
-  plain.in_gather_cols = plain.out_gather_cols = nullptr;
+  // no blocks / hints for the per-block passes: a block's own edge ids, no hub plan
   if (nz.size() <= 1) {
-    run_fast(&plain, nz.empty() ? walk : blocks[nz[0]], kind, RED_SUM, x, nullptr, w, w_map, out, F,
-             head_dim, s, epi);
+    run_fast(bare_walk(rw.wide, rw.ws, nz.empty() ? walk : rw.blocks[nz[0]]), kind, RED_SUM, x,
+             nullptr, w, w_map, out, F, head_dim, s, epi);
     return;
   }
-  DGLMIGraph no_ws;  // the ping-pong buffer must not alias the carry workspace
-  std::memset(&no_ws, 0, sizeof(no_ws));
-  Scratch tmp(&no_ws, walk.num_rows * F * static_cast<int64_t>(sizeof(float)), s);
+  // the ping-pong buffer must not alias the carry workspace
+  Scratch tmp(no_workspace(), walk.num_rows * F * static_cast<int64_t>(sizeof(float)), s);
   float* bufs[2] = {out, static_cast<float*>(tmp.ptr)};
   const int k = static_cast<int>(nz.size());
   const float* prev = epi ? epi->addend : nullptr;
@@ -331,26 +377,23 @@ void run_fast_blocked(const DGLMIGraph* g, const DGLMICsr* blocks, const DGLMICs
     e.bias = (epi && i == k - 1) ? epi->bias : nullptr;
     e.addend = prev;
     const bool any = e.row_mul || e.row_div || e.bias || e.addend;
-    run_fast(&plain, blocks[nz[i]], kind, RED_SUM, x, nullptr, w, w_map, dst, F, head_dim, s,
-             any ? &e : nullptr);
+    run_fast(bare_walk(rw.wide, rw.ws, rw.blocks[nz[i]]), kind, RED_SUM, x, nullptr, w, w_map, dst,
+             F, head_dim, s, any ? &e : nullptr);
     prev = dst;
   }
 }
 
-void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, const float* x,
-              const int32_t* x_map, const float* w, const int32_t* w_map, float* out, int64_t F,
-              int64_t head_dim, hipStream_t s, const DGLMIEpilogue* epi, const float* xr) {
+void run_fast(const ReduceWalk& rw, int kind, int red, const float* x, const int32_t* x_map,
+              const float* w, const int32_t* w_map, float* out, int64_t F, int64_t head_dim,
+              hipStream_t s, const DGLMIEpilogue* epi, const float* xr) {
+  const DGLMICsr& walk = rw.csr;
   // copy_u only: with an edge operand (u_mul_e) its per-edge gather by edge id
   // dominates and extra passes cost more than the smaller table saves (Reddit-size,
   // F = 64: copy_u_sum 3.88 -> 2.96 ms over 8 blocks, u_mul_e_sum 5.94 -> 7.23 ms)
-  if (g->num_col_blocks > 1 && !wide(g) && red == RED_SUM && x_map == nullptr && walk.nnz > 0 &&
-      kind == FAST_COPY_COL) {
-    const DGLMICsr* blocks = &walk == &g->in_csr ? g->in_col_blocks
-                             : (&walk == &g->out_csr ? g->out_col_blocks : nullptr);
-    if (blocks != nullptr) {
-      run_fast_blocked(g, blocks, walk, kind, x, w, w_map, out, F, head_dim, s, epi);
-      return;
-    }
+  if (rw.num_blocks > 1 && !rw.wide && red == RED_SUM && x_map == nullptr && walk.nnz > 0 &&
+      kind == FAST_COPY_COL && rw.blocks != nullptr) {
+    run_fast_blocked(rw, kind, x, w, w_map, out, F, head_dim, s, epi);
+    return;
   }
   if (walk.nnz == 0) {
     launch_fill(out, walk.num_rows * F, identity_of(red), s);
@@ -359,15 +402,10 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
   }
   FastArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.indptr = idx(g, walk.indptr);
+  a.indptr = rw.idx(walk.indptr);
   a.rows = walk.rows;
   a.indices = walk.indices;
-  // a position view's walk (DGLMIGraph.eid_identity), or an internal walk whose edge
-  // ids are its positions (data NULL: the R-GCN state's position-ordered walks): edge
-  // p's operand sits at p
-  const int id_bit = &walk == &g->in_csr ? 1 : (&walk == &g->out_csr ? 2 : 0);
-  a.eids = ((g->eid_identity & id_bit) != 0 || walk.data == nullptr) ? IdxPtr{nullptr, wide(g) ? 1 : 0}
-                                                                      : idx(g, walk.data);
+  a.eids = rw.idx(rw.eid_positions ? nullptr : walk.data);
   a.nnz = walk.nnz;
   a.num_rows = walk.num_rows;
   a.x = x;
@@ -380,14 +418,12 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
   a.chunk = fast_chunk_edges(walk.nnz, F);
   a.xr = xr;
   // cold-row hints: copy_u sum over a table larger than the Infinity Cache
-  if (kind == FAST_COPY_COL && red == RED_SUM && x_map == nullptr && fast_marked_supported(F)) {
-    const int32_t* marked = &walk == &g->in_csr ? g->in_gather_cols
-                            : (&walk == &g->out_csr ? g->out_gather_cols : nullptr);
-    if (marked != nullptr && walk.num_cols * F * static_cast<int64_t>(sizeof(float)) >= kMarkedMinTableBytes) {
-      a.indices = marked;
-      a.marked = 1;
-      a.num_cols = walk.num_cols;
-    }
+  if (kind == FAST_COPY_COL && red == RED_SUM && x_map == nullptr && fast_marked_supported(F) &&
+      rw.marked != nullptr &&
+      walk.num_cols * F * static_cast<int64_t>(sizeof(float)) >= kMarkedMinTableBytes) {
+    a.indices = rw.marked;
+    a.marked = 1;
+    a.num_cols = walk.num_cols;
   }
   if (epi) {
     a.row_mul = epi->row_mul;
@@ -401,15 +437,12 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
     kind = FAST_COL_MUL_POS;
   // hub plan: the same launch over the plan's walk (virtual rows first), hub rows' partials
   // in a scratch table of their own (not the carry workspace) and merged after the fixup
-  const DGLMIHubPlan* plan = &walk == &g->in_csr ? g->in_hub_plan
-                             : (&walk == &g->out_csr ? g->out_hub_plan : nullptr);
+  const DGLMIHubPlan* plan = rw.plan;
   if (plan != nullptr && !(kind == FAST_COPY_COL && red == RED_SUM && x_map == nullptr && epi == nullptr &&
-                           !wide(g) && fast_marked_supported(F) && plan->num_hubs > 0))
+                           !rw.wide && fast_marked_supported(F) && plan->num_hubs > 0))
     plan = nullptr;
-  DGLMIGraph no_ws;
-  std::memset(&no_ws, 0, sizeof(no_ws));
   const int64_t virt = plan ? plan->num_blocks * plan->num_hubs : 0;
-  Scratch part(&no_ws, virt * F * static_cast<int64_t>(sizeof(float)), s);
+  Scratch part(no_workspace(), virt * F * static_cast<int64_t>(sizeof(float)), s);
   if (plan != nullptr) {
     DGLMI_CHECK(plan->nnz == walk.nnz && plan->hub_nnz <= walk.nnz && plan->num_blocks >= 1 &&
                     plan->rows && plan->indices && plan->indptr && plan->hub_rows,
@@ -428,7 +461,7 @@ void run_fast(const DGLMIGraph* g, const DGLMICsr& walk, int kind, int red, cons
     a.hub_nnz = plan->hub_nnz;
   }
   const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, F);
-  Scratch carry(g, lay.bytes, s);
+  Scratch carry(rw.ws, lay.bytes, s);
   lay.point(a, carry.ptr);
   launch_fast_reduce(kind, red, a, s);
   check_hip(hipGetLastError(), "fast reduce launch");
@@ -485,6 +518,52 @@ EdgeArgs base_args(const DGLMIGraph* g, const DGLMICsr& walk) {
   return a;
 }
 
+// The feature shape of a forward or backward call: D output values per row, each the
+// reduction of `len` products (dot: the vector length; else 1), through `binfo` when
+// the operands broadcast (bc).
+struct ReduceShape {
+  bool bc;
+  Bcast binfo;
+  int64_t D, len;
+};
+
+ReduceShape reduce_shape(int op, const DGLMIArray* lhs, const DGLMIArray* rhs) {
+  ReduceShape r;
+  std::memset(&r, 0, sizeof(r));
+  r.len = 1;
+  if (op == OP_USE_LHS) {
+    r.D = feat_numel(lhs);
+  } else if (has_bcast(lhs, rhs)) {
+    r.bc = true;
+    r.binfo = calc_bcast(op, lhs, rhs, nullptr);
+    r.D = r.binfo.out_len;
+    r.len = r.binfo.data_len;
+  } else {
+    if (!valid_elementwise(lhs, rhs))
+      throw Error("Cannot compute binary operation between feature shapes " + shape_str(lhs) +
+                  " and " + shape_str(rhs));
+    r.len = op == OP_DOT ? lhs->shape[lhs->ndim - 1] : 1;
+    r.D = op == OP_DOT ? (r.len ? feat_numel(lhs) / r.len : 0) : feat_numel(lhs);
+  }
+  return r;
+}
+
+// u_mul_e on the load-balanced kernels: the FAST_COL_MUL_EDGE* kind of the operand
+// shapes (and the broadcast kinds' head width), or -1
+int mul_edge_kind(bool bc, const Bcast& binfo, int64_t* head_dim) {
+  if (!bc) return FAST_COL_MUL_EDGE;
+  if (binfo.ndim == 2 && binfo.rhs_shape[1] == 1 && binfo.lhs_shape[0] == binfo.rhs_shape[0] &&
+      binfo.lhs_shape[1] == binfo.out_shape[1]) {
+    *head_dim = binfo.lhs_shape[1];
+    return FAST_COL_MUL_EDGE_BCAST;  // (N, H, D) x (E, H, 1): GAT aggregation
+  }
+  if (binfo.ndim == 1 && binfo.rhs_shape[0] == 1) {
+    *head_dim = binfo.lhs_shape[0];
+    return FAST_COL_MUL_EDGE_BCAST;  // (N, D) x (E, 1)
+  }
+  return -1;
+}
+
 // ---------------------------------------------------------------------------
 // Forward: BinaryOpReduce / CopyReduce
 // ---------------------------------------------------------------------------
@@ -510,31 +589,9 @@ void forward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const D
     }
   }
   const DGLMICsr& walk = g->in_csr;  // reductions go to dst; edges enumerated on the in-CSR
-  check_csr(walk, "in_csr", red == RED_NONE || true, wide(g));
+  check_csr(walk, "in_csr", true, wide(g));
 
-  bool bc = false;
-  Bcast binfo;
-  std::memset(&binfo, 0, sizeof(binfo));
-  int64_t D, len = 1;
-  if (op == OP_USE_LHS) {
-    D = feat_numel(lhs);
-  } else if (has_bcast(lhs, rhs)) {
-    bc = true;
-    binfo = calc_bcast(op, lhs, rhs, nullptr);
-    D = binfo.out_len;
-    len = binfo.data_len;
-  } else {
-    if (!valid_elementwise(lhs, rhs))
-      throw Error("Cannot compute binary operation between feature shapes " + shape_str(lhs) +
-                  " and " + shape_str(rhs));
-    if (op == OP_DOT) {
-      len = lhs->shape[lhs->ndim - 1];
-      D = feat_numel(lhs) / std::max<int64_t>(len, 1);
-      if (len == 0) D = 0;
-    } else {
-      D = feat_numel(lhs);
-    }
-  }
+  const auto [bc, binfo, D, len] = reduce_shape(op, lhs, rhs);
   DGLMI_CHECK(feat_numel(out) == D, "out feature size " + std::to_string(feat_numel(out)) +
                                         " != expected " + std::to_string(D));
   const int64_t out_rows = out->shape[0];
@@ -551,24 +608,15 @@ void forward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const D
     if (op == OP_USE_LHS && lhs_t == DGLMI_TARGET_SRC) kind = FAST_COPY_COL;
     else if (op == OP_USE_LHS && lhs_t == DGLMI_TARGET_EDGE) kind = FAST_COPY_EDGE;
     else if (op == OP_MUL && red == RED_SUM && lhs_t == DGLMI_TARGET_SRC &&
-             rhs_t == DGLMI_TARGET_EDGE && aligned16(rhs->data)) {
-      if (!bc) {
-        kind = FAST_COL_MUL_EDGE;
-      } else if (binfo.ndim == 2 && binfo.rhs_shape[1] == 1 && binfo.lhs_shape[0] == binfo.rhs_shape[0] &&
-                 binfo.lhs_shape[1] == binfo.out_shape[1]) {
-        kind = FAST_COL_MUL_EDGE_BCAST;  // (N, H, D) x (E, H, 1): GAT aggregation
-        head_dim = binfo.lhs_shape[1];
-      } else if (binfo.ndim == 1 && binfo.rhs_shape[0] == 1) {
-        kind = FAST_COL_MUL_EDGE_BCAST;  // (N, D) x (E, 1)
-        head_dim = binfo.lhs_shape[0];
-      }
-    }
+             rhs_t == DGLMI_TARGET_EDGE && aligned16(rhs->data))
+      kind = mul_edge_kind(bc, binfo, &head_dim);
     if (kind >= 0 && fast_supported(kind, D, head_dim) && walk.rows != nullptr) {
       const float* w = (kind == FAST_COL_MUL_EDGE || kind == FAST_COL_MUL_EDGE_BCAST) ? rhs->data : nullptr;
       const bool epi_ok = epi == nullptr || ((epi->bias == nullptr || aligned16(epi->bias)) &&
                                              (epi->addend == nullptr || aligned16(epi->addend)));
       if (epi_ok) {
-        run_fast(g, walk, kind, red, lhs->data, lhs_map, w, rhs_map, out->data, D, head_dim, s, epi);
+        run_fast(graph_walk(g, true), kind, red, lhs->data, lhs_map, w, rhs_map, out->data, D, head_dim,
+                 s, epi);
         return;
       }
     }
@@ -611,20 +659,18 @@ void forward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const D
   if (red != RED_NONE && walk.rows != nullptr && generic_lb_supported(D)) {
     if (walk.nnz == 0) {
       if (!need_fill) launch_fill(out->data, walk.num_rows * D, identity_of(red), s);
-      if (epi) launch_epilogue(out->data, out_rows, D, epi->row_mul, epi->row_div, epi->bias, epi->addend, s);
-      return;
+    } else {
+      a.chunk = fast_chunk_edges(walk.nnz, D);
+      const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, D);
+      Scratch carry(caller_workspace(g), lay.bytes, s);
+      lay.point(a, carry.ptr);
+      launch_generic_lb(op, red, bc, false, a, s);
+      check_hip(hipGetLastError(), "generic lb forward launch");
     }
-    a.chunk = fast_chunk_edges(walk.nnz, D);
-    const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, D);
-    Scratch carry(g, lay.bytes, s);
-    lay.point(a, carry.ptr);
-    launch_generic_lb(op, red, bc, false, a, s);
-    check_hip(hipGetLastError(), "generic lb forward launch");
-    if (epi) launch_epilogue(out->data, out_rows, D, epi->row_mul, epi->row_div, epi->bias, epi->addend, s);
-    return;
+  } else {
+    launch_generic_forward(op, red, bc, a, s);
+    check_hip(hipGetLastError(), "generic forward launch");
   }
-  launch_generic_forward(op, red, bc, a, s);
-  check_hip(hipGetLastError(), "generic forward launch");
   if (epi) launch_epilogue(out->data, out_rows, D, epi->row_mul, epi->row_div, epi->bias, epi->addend, s);
 }
 
@@ -660,24 +706,7 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
   const DGLMICsr& walk = walk_in ? g->in_csr : g->out_csr;
   check_csr(walk, walk_in ? "in_csr" : "out_csr", x_t == DGLMI_TARGET_EDGE, wide(g));
 
-  bool bc = false;
-  Bcast binfo;
-  std::memset(&binfo, 0, sizeof(binfo));
-  int64_t D, len = 1;
-  if (op == OP_USE_LHS) {
-    D = feat_numel(lhs);
-  } else if (has_bcast(lhs, rhs)) {
-    bc = true;
-    binfo = calc_bcast(op, lhs, rhs, nullptr);
-    D = binfo.out_len;
-    len = binfo.data_len;
-  } else {
-    if (!valid_elementwise(lhs, rhs))
-      throw Error("Cannot compute binary operation between feature shapes " + shape_str(lhs) +
-                  " and " + shape_str(rhs));
-    len = op == OP_DOT ? lhs->shape[lhs->ndim - 1] : 1;
-    D = op == OP_DOT ? (len ? feat_numel(lhs) / len : 0) : feat_numel(lhs);
-  }
+  const auto [bc, binfo, D, len] = reduce_shape(op, lhs, rhs);
   DGLMI_CHECK(feat_numel(out) == D && feat_numel(grad_out) == D, "out / grad_out feature size mismatch");
   const int64_t Dg = D * len;
   DGLMI_CHECK(feat_numel(grad) == Dg, "grad feature size " + std::to_string(feat_numel(grad)) +
@@ -704,19 +733,11 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
     } else if (op == OP_MUL && want == 0 && rhs_t == DGLMI_TARGET_EDGE && aligned16(rhs->data)) {
       w = rhs->data;
       w_map = rhs_map;
-      if (!bc) {
-        kind = FAST_COL_MUL_EDGE;
-      } else if (binfo.ndim == 2 && binfo.rhs_shape[1] == 1 && binfo.lhs_shape[0] == binfo.rhs_shape[0] &&
-                 binfo.lhs_shape[1] == binfo.out_shape[1]) {
-        kind = FAST_COL_MUL_EDGE_BCAST;
-        head_dim = binfo.lhs_shape[1];
-      } else if (binfo.ndim == 1 && binfo.rhs_shape[0] == 1) {
-        kind = FAST_COL_MUL_EDGE_BCAST;
-        head_dim = binfo.lhs_shape[0];
-      }
+      kind = mul_edge_kind(bc, binfo, &head_dim);
     }
     if (kind >= 0 && fast_supported(kind, D, head_dim)) {
-      run_fast(g, walk, kind, RED_SUM, grad_out->data, nullptr, w, w_map, grad->data, D, head_dim, s);
+      run_fast(graph_walk(g, walk_in), kind, RED_SUM, grad_out->data, nullptr, w, w_map, grad->data, D,
+               head_dim, s);
       return;
     }
   }
@@ -730,8 +751,8 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
   if (red == RED_NONE && (op == OP_ADD || (op == OP_SUB && want == 0)) && !bc &&
       x_t != DGLMI_TARGET_EDGE && !need_fill && out_map == nullptr && walk.rows != nullptr &&
       aligned16(grad->data) && aligned16(grad_out->data) && fast_supported(FAST_COPY_EDGE, D, 1)) {
-    run_fast(g, walk, FAST_COPY_EDGE, RED_SUM, grad_out->data, nullptr, nullptr, nullptr, grad->data,
-             D, 1, s);
+    run_fast(graph_walk(g, walk_in), FAST_COPY_EDGE, RED_SUM, grad_out->data, nullptr, nullptr,
+             nullptr, grad->data, D, 1, s);
     return;
   }
 
@@ -743,8 +764,8 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
       !need_fill && out_map == nullptr && lhs_map == nullptr && walk.rows != nullptr &&
       aligned16(grad->data) && aligned16(grad_out->data) && aligned16(out->data) &&
       aligned16(lhs->data) && fast_supported(FAST_COL_TIE, D, 1)) {
-    run_fast(g, walk, FAST_COL_TIE, RED_SUM, grad_out->data, nullptr, out->data, nullptr, grad->data,
-             D, 1, s, nullptr, lhs->data);
+    run_fast(graph_walk(g, walk_in), FAST_COL_TIE, RED_SUM, grad_out->data, nullptr, out->data,
+             nullptr, grad->data, D, 1, s, nullptr, lhs->data);
     return;
   }
 
@@ -795,7 +816,7 @@ void backward(int red, int op, const DGLMIGraph* g, int lhs_t, int rhs_t, const 
     }
     a.chunk = fast_chunk_edges(walk.nnz, Dg);
     const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, Dg);
-    Scratch carry(g, lay.bytes, s);
+    Scratch carry(caller_workspace(g), lay.bytes, s);
     lay.point(a, carry.ptr);
     launch_generic_lb(op, red, bc, true, a, s);
     check_hip(hipGetLastError(), "generic lb backward launch");
@@ -1180,7 +1201,7 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
     }
     const int64_t part_bytes = (part_floats * static_cast<int64_t>(sizeof(float)) + 255) & ~int64_t(255);
     const CarryLayout lay(max_chunks, cw);  // after the partial tables
-    Scratch ws(graph, part_bytes + lay.bytes, s);
+    Scratch ws(caller_workspace(graph), part_bytes + lay.bytes, s);
     // [out parts][lf parts][m parts][l parts][ls parts]: the float4 arrays first
     float* out_part = static_cast<float*>(ws.ptr);
     float* lf_part = lf ? out_part + nb * N * a.F : nullptr;
@@ -1212,7 +1233,7 @@ int gat_forward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const 
     return 0;
   }
   const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, cw);
-  Scratch carry(graph, lay.bytes, s);
+  Scratch carry(caller_workspace(graph), lay.bytes, s);
   lay.point(a, carry.ptr);
   launch_gat_forward(a, s);
   check_hip(hipGetLastError(), "fused GAT forward launch");
@@ -1308,7 +1329,7 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     }
   const int64_t stats_bytes = a.num_rows * a.H * 16;
   const CarryLayout lay(chunks, a.F + a.H);  // after the stats, rounded up to 256 B
-  Scratch ws(graph, stats_bytes + lay.bytes + 256, s);
+  Scratch ws(caller_workspace(graph), stats_bytes + lay.bytes + 256, s);
   a.stats = static_cast<float4*>(ws.ptr);
   lay.point(a, static_cast<char*>(ws.ptr) + ((stats_bytes + 255) & ~int64_t(255)));
   if (lf_in != nullptr) {
@@ -1335,23 +1356,18 @@ int gat_backward_impl(const DGLMIGraph* graph, const DGLMIArray* feat_src, const
     return 0;
   }
   if (pos_path) {
-    DGLMIGraph nows;  // t must not alias the caller's workspace (the reduce's carries)
-    std::memset(&nows, 0, sizeof(nows));
-    Scratch tbuf(&nows, in.nnz * a.H * static_cast<int64_t>(sizeof(float)), s);
+    // t must not alias the caller's workspace (the reduce's carries)
+    Scratch tbuf(no_workspace(), in.nnz * a.H * static_cast<int64_t>(sizeof(float)), s);
     a.t = static_cast<float*>(tbuf.ptr);
     launch_gat_stats(a, s);
     GatArgs b = a;
     gat_set_csr(b, outc, gat_bwd_chunk_edges);  // eids: read by the dropout instances only
     launch_gat_backward_src(b, s);
     check_hip(hipGetLastError(), "fused GAT backward (src) launch");
-    DGLMIGraph gp = *graph;  // no blocks / hints for the gather-sum
-    gp.num_col_blocks = 0;
-    gp.in_col_blocks = gp.out_col_blocks = nullptr;
-    gp.in_gather_cols = gp.out_gather_cols = nullptr;
-    DGLMICsr walk = in;
+    DGLMICsr walk = in;  // no blocks / hints for the gather-sum
     walk.data = graph->gat_edge_pos;
-    run_fast(&gp, walk, FAST_COPY_EDGE, RED_SUM, a.t, nullptr, nullptr, nullptr, grad_er->data, a.H,
-             1, s);
+    run_fast(bare_walk(graph, walk), FAST_COPY_EDGE, RED_SUM, a.t, nullptr, nullptr, nullptr,
+             grad_er->data, a.H, 1, s);
     return 0;
   }
   if (nb > 1) {
@@ -1614,10 +1630,8 @@ int DGLMIFusedGatKernel(const DGLMIGraph* graph, const DGLMIArray* feat_src, con
       throw Error(g_last_error);
     }
   } else {
-    DGLMIGraph no_ws = *graph;  // the max must not alias the kernels' workspace
-    no_ws.workspace = nullptr;
-    no_ws.workspace_bytes = 0;
-    Scratch mx(&no_ws, N * H * static_cast<int64_t>(sizeof(float)), s);
+    // the max must not alias the kernels' workspace
+    Scratch mx(no_workspace(), N * H * static_cast<int64_t>(sizeof(float)), s);
     DGLMIArray m = gat_state_view(static_cast<float*>(mx.ptr), N, H);
     if (DGLMIFusedGatForward(graph, feat_src, el, er, slope, ret, &m, &l, stream) != 0)
       throw Error(g_last_error);
@@ -1654,10 +1668,7 @@ int DGLMIKernelBackwardFusedGat(const DGLMIGraph* graph, const DGLMIArray* feat_
     }
   } else {
     // sum holds max + log(sum): attention = exp(s - lse) / 1
-    DGLMIGraph no_ws = *graph;
-    no_ws.workspace = nullptr;
-    no_ws.workspace_bytes = 0;
-    Scratch ones(&no_ws, N * H * static_cast<int64_t>(sizeof(float)), s);
+    Scratch ones(no_workspace(), N * H * static_cast<int64_t>(sizeof(float)), s);
     launch_fill(static_cast<float*>(ones.ptr), N * H, 1.0f, s);
     const DGLMIArray m = gat_state_view(sum->data, N, H);
     const DGLMIArray l = gat_state_view(static_cast<float*>(ones.ptr), N, H);
@@ -1780,7 +1791,7 @@ int softmax_forward(const DGLMIGraph* graph, const DGLMIArray* logits, DGLMIArra
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.nnz == 0) return 0;
-  Scratch ws(graph, DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
+  Scratch ws(caller_workspace(graph), DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
   softmax_layout(a, ws.ptr, true);
   a.s = logits->data;
   a.out = out->data;
@@ -1812,7 +1823,7 @@ int softmax_backward(const DGLMIGraph* graph, const DGLMIArray* out, const DGLMI
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.nnz == 0) return 0;
-  Scratch ws(graph, DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
+  Scratch ws(caller_workspace(graph), DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
   softmax_layout(a, ws.ptr, true);
   a.s = out->data;
   a.ga = grad_out->data;
@@ -1869,7 +1880,7 @@ int DGLMIEdgeSoftmaxNodeLogitsForward(const DGLMIGraph* graph, const DGLMIArray*
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.nnz == 0) return 0;
-  Scratch ws(graph, DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
+  Scratch ws(caller_workspace(graph), DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
   softmax_layout(a, ws.ptr, true);
   a.s = nullptr;
   a.out = out->data;
@@ -1895,7 +1906,7 @@ int DGLMIEdgeSoftmaxNodeLogitsForwardEx(const DGLMIGraph* graph, const DGLMIArra
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.nnz == 0) return 0;
-  Scratch ws(graph, DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
+  Scratch ws(caller_workspace(graph), DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
   // the row statistics straight into the caller's buffers
   a.stat0 = row_max->data;
   a.stat1 = row_sum->data;
@@ -1926,7 +1937,7 @@ int DGLMIEdgeSoftmaxNodeLogitsBackward(const DGLMIGraph* graph, const DGLMIArray
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.nnz == 0) return 0;
-  Scratch ws(graph, DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
+  Scratch ws(caller_workspace(graph), DGLMIEdgeSoftmaxWorkspaceBytes(&graph->in_csr, H), s);
   softmax_layout(a, ws.ptr, true);
   a.s = out->data;
   a.ga = grad_out->data;
@@ -2038,20 +2049,6 @@ int DGLMIEdgeSoftmaxLeakyBackward(const DGLMIGraph* graph, const DGLMIArray* out
 // ---------------------------------------------------------------------------
 namespace {
 
-DGLMIGraph plain_graph(const DGLMIGraph* g) {
-  DGLMIGraph p = *g;
-  p.num_col_blocks = 0;
-  p.in_col_blocks = p.out_col_blocks = nullptr;
-  p.in_gather_cols = p.out_gather_cols = nullptr;
-  return p;
-}
-
-DGLMIGraph no_workspace() {
-  DGLMIGraph z;
-  std::memset(&z, 0, sizeof(z));
-  return z;
-}
-
 int64_t edge_values(const DGLMIArray* norm, int64_t E, const char* name) {
   check_array(norm, name);
   const int64_t n = norm->shape[0] * feat_numel(norm);
@@ -2062,14 +2059,14 @@ int64_t edge_values(const DGLMIArray* norm, int64_t E, const char* name) {
 // the out-CSR regrouped by relation-expanded source row (mode 0: t * N + u, mode
 // 1: u * R + t), stable: positions of a row keep their out-CSR order
 struct TypedOutCsr {
-  DGLMIGraph z = no_workspace();
   Scratch keys, ptr, idx, dat, rows, ws;
   DGLMICsr csr;
   TypedOutCsr(const DGLMICsr& out, const int32_t* etypes, int64_t num_typed_rows, int64_t mul,
               int mode, hipStream_t s)
-      : keys(&z, out.nnz * 4, s), ptr(&z, (num_typed_rows + 1) * 4, s), idx(&z, out.nnz * 4, s),
-        dat(&z, out.nnz * 4, s), rows(&z, out.nnz * 4, s),
-        ws(&z, DGLMICOOToCSRDeviceWorkspaceBytes(num_typed_rows, out.nnz), s) {
+      : keys(no_workspace(), out.nnz * 4, s), ptr(no_workspace(), (num_typed_rows + 1) * 4, s),
+        idx(no_workspace(), out.nnz * 4, s), dat(no_workspace(), out.nnz * 4, s),
+        rows(no_workspace(), out.nnz * 4, s),
+        ws(no_workspace(), DGLMICOOToCSRDeviceWorkspaceBytes(num_typed_rows, out.nnz), s) {
     launch_typed_ids(out.rows, out.data, etypes, out.nnz, mul, mode, static_cast<int32_t*>(keys.ptr),
                      s);
     DGLMI_CHECK(DGLMICOOToCSRDevice(num_typed_rows, out.nnz, static_cast<int32_t*>(keys.ptr),
@@ -2175,21 +2172,20 @@ int DGLMIRgcnLayer0(const DGLMIGraph* graph, const DGLMIArray* weight,
   check_fast_width(F);
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DGLMIGraph z = no_workspace(), pg = plain_graph(graph);
   if (const DGLMIRgcnState* st = rgcn_state(graph, R, N, 0)) {
     const float* w = nullptr;
     const DGLMICsr walk = rgcn_in_walk(graph, st, 0, R * N, norm->data, &w);
-    run_fast(&pg, walk, FAST_COL_MUL_EDGE_BCAST, RED_SUM, weight->data, nullptr, w, nullptr,
-             ret->data, F, F, s);
+    run_fast(bare_walk(graph, walk), FAST_COL_MUL_EDGE_BCAST, RED_SUM, weight->data, nullptr, w,
+             nullptr, ret->data, F, F, s);
     return 0;
   }
-  Scratch cols(&z, in.nnz * 4, s);
+  Scratch cols(no_workspace(), in.nnz * 4, s);
   launch_typed_ids(in.indices, in.data, etypes, in.nnz, N, 0, static_cast<int32_t*>(cols.ptr), s);
   DGLMICsr walk = in;
   walk.indices = static_cast<int32_t*>(cols.ptr);
   walk.num_cols = R * N;
-  run_fast(&pg, walk, FAST_COL_MUL_EDGE_BCAST, RED_SUM, weight->data, nullptr, norm->data, nullptr,
-           ret->data, F, F, s);
+  run_fast(bare_walk(graph, walk), FAST_COL_MUL_EDGE_BCAST, RED_SUM, weight->data, nullptr,
+           norm->data, nullptr, ret->data, F, F, s);
   API_END();
 }
 
@@ -2211,7 +2207,6 @@ int DGLMIRgcnLayer0Backward(const DGLMIGraph* graph,
   check_fast_width(F);
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DGLMIGraph pg = plain_graph(graph);
   if (out.nnz == 0) {
     launch_fill(grad_weight->data, R * N * F, 0.0f, s);
     return 0;
@@ -2219,13 +2214,13 @@ int DGLMIRgcnLayer0Backward(const DGLMIGraph* graph,
   if (const DGLMIRgcnState* st = rgcn_state(graph, R, N, 0)) {
     const float* w = nullptr;
     const DGLMICsr walk = rgcn_out_walk(st, 0, norm->data, &w);
-    run_fast(&pg, walk, FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, w, nullptr,
-             grad_weight->data, F, F, s);
+    run_fast(bare_walk(graph, walk), FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, w,
+             nullptr, grad_weight->data, F, F, s);
     return 0;
   }
   TypedOutCsr typed(out, etypes, R * N, N, 0, s);
-  run_fast(&pg, typed.csr, FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, norm->data,
-           nullptr, grad_weight->data, F, F, s);
+  run_fast(bare_walk(graph, typed.csr), FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr,
+           norm->data, nullptr, grad_weight->data, F, F, s);
   API_END();
 }
 
@@ -2265,7 +2260,6 @@ int rgcn_layer1_impl(const DGLMIGraph* graph, const DGLMIArray* hidden,
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t N = in.num_cols, M = R * X;
-  DGLMIGraph z = no_workspace(), pg = plain_graph(graph);
   if (const DGLMIRgcnState* fs = rgcn_state(graph, R, N, 2)) {
     if (rgcn_fused_ok(K, X, R + (loop != nullptr)) && aligned16(hidden->data) && in.nnz > 0) {
       const int32_t* eids = nullptr;
@@ -2279,7 +2273,8 @@ int rgcn_layer1_impl(const DGLMIGraph* graph, const DGLMIArray* hidden,
     }
   }
   const DGLMIRgcnState* st = rgcn_state(graph, R, N, 1);
-  Scratch wcat(&z, K * M * 4, s), y(&z, N * M * 4, s), cols(&z, st ? 0 : in.nnz * 4, s);
+  Scratch wcat(no_workspace(), K * M * 4, s), y(no_workspace(), N * M * 4, s),
+      cols(no_workspace(), st ? 0 : in.nnz * 4, s);
   launch_permute_rkx(weight->data, R, K, X, true, static_cast<float*>(wcat.ptr), s);
   // y[u, r * X + x] = sum_k hidden[u, k] w[r, k, x]; row u * R + r of the (N R, X) view
   launch_gemm(hidden->data, K, 1, static_cast<float*>(wcat.ptr), M, 1, static_cast<float*>(y.ptr), N,
@@ -2294,7 +2289,7 @@ int rgcn_layer1_impl(const DGLMIGraph* graph, const DGLMIArray* hidden,
     walk.num_cols = N * R;
   }
   // the self-loop message hidden . loop (+ the caller's addend) enters as the addend
-  Scratch lt(&z, loop ? N * X * 4 : 0, s);
+  Scratch lt(no_workspace(), loop ? N * X * 4 : 0, s);
   if (loop) {
     launch_gemm(hidden->data, K, 1, loop->data, X, 1, static_cast<float*>(lt.ptr), N, X, K, 1,
                 nullptr, s);
@@ -2302,8 +2297,8 @@ int rgcn_layer1_impl(const DGLMIGraph* graph, const DGLMIArray* hidden,
     addend = static_cast<const float*>(lt.ptr);
   }
   const DGLMIEpilogue e2{nullptr, nullptr, bias, addend};
-  run_fast(&pg, walk, FAST_COL_MUL_EDGE_BCAST, RED_SUM, static_cast<float*>(y.ptr), nullptr, w,
-           nullptr, ret->data, X, X, s, (bias || addend) ? &e2 : nullptr);
+  run_fast(bare_walk(graph, walk), FAST_COL_MUL_EDGE_BCAST, RED_SUM, static_cast<float*>(y.ptr),
+           nullptr, w, nullptr, ret->data, X, X, s, (bias || addend) ? &e2 : nullptr);
   API_END();
 }
 }  // namespace
@@ -2354,7 +2349,6 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
   }
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DGLMIGraph z = no_workspace(), pg = plain_graph(graph);
   const DGLMIRgcnState* fs = out.nnz > 0 ? rgcn_state(graph, R, N, 2) : nullptr;
   const bool fused = fs && rgcn_fused_ok(X, K, R + (loop != nullptr)) &&
                      aligned16(grad_out->data) && fs->out_typed[0].indptr;
@@ -2363,9 +2357,9 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
   const int64_t MG = fused && loop ? M + X : M;
   const int64_t splits = gemm_splits(K, MG, N);
   const int64_t lsplits = grad_loop && !fused ? gemm_splits(K, X, N) : 1;
-  Scratch gy(&z, N * MG * 4, s), gw(&z, K * MG * 4, s),
-      parts(&z, std::max(splits > 1 ? splits * K * MG * 4 : 0, lsplits > 1 ? lsplits * K * X * 4 : 0),
-            s);
+  Scratch gy(no_workspace(), N * MG * 4, s), gw(no_workspace(), K * MG * 4, s),
+      parts(no_workspace(),
+            std::max(splits > 1 ? splits * K * MG * 4 : 0, lsplits > 1 ? lsplits * K * X * 4 : 0), s);
   // grad_loop = hidden^T (K x N) . grad_out (N x X), split over N
   auto loop_weight_grad = [&]() {
     if (grad_loop)
@@ -2388,7 +2382,7 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
       launch_permute_rkx(static_cast<float*>(gw.ptr), R, K, X, false, grad_weight->data, s);
     } else {
       // gw (K x (R + 1) X) -> [R + 1][K][X]: the relation blocks, then the self-loop one
-      Scratch gp(&z, (R + 1) * K * X * 4, s);
+      Scratch gp(no_workspace(), (R + 1) * K * X * 4, s);
       float* p = static_cast<float*>(gp.ptr);
       launch_permute_rkx(static_cast<float*>(gw.ptr), R + 1, K, X, false, p, s);
       check_hip(hipMemcpyAsync(grad_weight->data, p, R * K * X * 4, hipMemcpyDeviceToDevice, s),
@@ -2400,18 +2394,18 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
     check_hip(hipGetLastError(), "rgcn fused layer1 backward launch");
     return 0;
   }
-  Scratch wcat(&z, K * M * 4, s);
+  Scratch wcat(no_workspace(), K * M * 4, s);
   launch_permute_rkx(weight->data, R, K, X, true, static_cast<float*>(wcat.ptr), s);
   // gy[u * R + t] = sum over out-edges of u with type t of norm_e * grad_out[v]
   if (const DGLMIRgcnState* st = out.nnz > 0 ? rgcn_state(graph, R, N, 1) : nullptr) {
     const float* w = nullptr;
     const DGLMICsr walk = rgcn_out_walk(st, 1, norm->data, &w);
-    run_fast(&pg, walk, FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, w, nullptr,
-             static_cast<float*>(gy.ptr), X, X, s);
+    run_fast(bare_walk(graph, walk), FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, w,
+             nullptr, static_cast<float*>(gy.ptr), X, X, s);
   } else if (out.nnz > 0) {
     TypedOutCsr typed(out, etypes, N * R, R, 1, s);
-    run_fast(&pg, typed.csr, FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr, norm->data,
-             nullptr, static_cast<float*>(gy.ptr), X, X, s);
+    run_fast(bare_walk(graph, typed.csr), FAST_COL_MUL_EDGE_BCAST, RED_SUM, grad_out->data, nullptr,
+             norm->data, nullptr, static_cast<float*>(gy.ptr), X, X, s);
   } else {
     launch_fill(static_cast<float*>(gy.ptr), N * M, 0.0f, s);
   }
@@ -2423,7 +2417,7 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
               M, N, splits, static_cast<float*>(parts.ptr), s);
   launch_permute_rkx(static_cast<float*>(gw.ptr), R, K, X, false, grad_weight->data, s);
   if (loop && grad_hidden) {  // grad_hidden += grad_out . loop^T
-    Scratch lt(&z, N * K * 4, s);
+    Scratch lt(no_workspace(), N * K * 4, s);
     launch_gemm(grad_out->data, X, 1, loop->data, 1, X, static_cast<float*>(lt.ptr), N, K, X, 1,
                 nullptr, s);
     launch_add_into(grad_hidden->data, static_cast<float*>(lt.ptr), N * K, s);
@@ -2501,7 +2495,6 @@ int DGLMIRgcnPrepare(const DGLMIGraph* graph, const DGLMIArray* norm,
   float* in_norm = norm ? reinterpret_cast<float*>(take(e4)) : nullptr;
   launch_iota_i32(positions, E, s);
   if (norm) launch_gather_f32(norm->data, in.data, E, in_norm, s);
-  DGLMIGraph z = no_workspace();
   for (int layer = 0; layer < 2; ++layer) {
     if (!(layer == 0 ? want0 : want1)) continue;
     const int64_t mul = layer == 0 ? N : R;
@@ -2514,7 +2507,7 @@ int DGLMIRgcnPrepare(const DGLMIGraph* graph, const DGLMIArray* norm,
     launch_typed_ids(in.indices, in.data, etypes, E, mul, layer, cols, s);
     // the out-CSR regrouped by the same key, stable (TypedOutCsr, kept)
     const int64_t ws_bytes = DGLMICOOToCSRDeviceWorkspaceBytes(R * N, E);
-    Scratch keys(&z, E * 4, s), ws(&z, ws_bytes, s);
+    Scratch keys(no_workspace(), E * 4, s), ws(no_workspace(), ws_bytes, s);
     launch_typed_ids(out.rows, out.data, etypes, E, mul, layer, static_cast<int32_t*>(keys.ptr), s);
     DGLMI_CHECK(DGLMICOOToCSRDevice(R * N, E, static_cast<int32_t*>(keys.ptr), out.indices, out.data,
                                     ptr, idx, dat, ws.ptr, ws_bytes, s) == 0,
@@ -2543,7 +2536,7 @@ int DGLMIRgcnPrepare(const DGLMIGraph* graph, const DGLMIArray* norm,
     int32_t* rows = reinterpret_cast<int32_t*>(take(e4));
     float* rnorm = norm ? reinterpret_cast<float*>(take(e4)) : nullptr;
     const int64_t ws_bytes = DGLMICOOToCSRDeviceWorkspaceBytes(R * nd, E);
-    Scratch keys(&z, E * 4, s), ws(&z, ws_bytes, s);
+    Scratch keys(no_workspace(), E * 4, s), ws(no_workspace(), ws_bytes, s);
     launch_typed_ids(in.rows, in.data, etypes, E, nd, 0, static_cast<int32_t*>(keys.ptr), s);
     DGLMI_CHECK(DGLMICOOToCSRDevice(R * nd, E, static_cast<int32_t*>(keys.ptr), in.indices, in.data,
                                     ptr, idx, dat, ws.ptr, ws_bytes, s) == 0,
@@ -2624,8 +2617,7 @@ int DGLMINbAccess(const DGLMIGraph* graph, const DGLMIArray* feat, const int32_t
   DGLMI_CHECK(fast_supported(FAST_COPY_COL, F, 1), "unsupported feature width");
   DeviceGuard guard(graph->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  DGLMIGraph z = no_workspace();
-  Scratch sink(&z, in.num_rows * F * 4, s);
+  Scratch sink(no_workspace(), in.num_rows * F * 4, s);
   // destroyed on every path, a throwing check or launch included
   struct Events {
     hipEvent_t a = nullptr, b = nullptr;
@@ -2639,7 +2631,7 @@ int DGLMINbAccess(const DGLMIGraph* graph, const DGLMIArray* feat, const int32_t
   double total = 0.0;
   for (int i = 0; i < times; ++i) {
     check_hip(hipEventRecord(ev.a, s), "hipEventRecord");
-    run_fast(graph, in, FAST_COPY_COL, RED_SUM, feat->data, nullptr, nullptr, nullptr,
+    run_fast(graph_walk(graph, true), FAST_COPY_COL, RED_SUM, feat->data, nullptr, nullptr, nullptr,
              static_cast<float*>(sink.ptr), F, 1, s);
     check_hip(hipEventRecord(ev.b, s), "hipEventRecord");
     check_hip(hipEventSynchronize(ev.b), "hipEventSynchronize");
