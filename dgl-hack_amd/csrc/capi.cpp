@@ -439,13 +439,15 @@ void run_fast(const ReduceWalk& rw, int kind, int red, const float* x, const int
   // in a scratch table of their own (not the carry workspace) and merged after the fixup
   const DGLMIHubPlan* plan = rw.plan;
   if (plan != nullptr && !(kind == FAST_COPY_COL && red == RED_SUM && x_map == nullptr && epi == nullptr &&
-                           !rw.wide && fast_marked_supported(F) && plan->num_hubs > 0))
+                           !rw.wide && fast_marked_supported(F) && plan->num_hubs > 0 &&
+                           a.chunk <= kPlanMaxChunk))
     plan = nullptr;
   const int64_t virt = plan ? plan->num_blocks * plan->num_hubs : 0;
   Scratch part(no_workspace(), virt * F * static_cast<int64_t>(sizeof(float)), s);
   if (plan != nullptr) {
     DGLMI_CHECK(plan->nnz == walk.nnz && plan->hub_nnz <= walk.nnz && plan->num_blocks >= 1 &&
-                    plan->rows && plan->indices && plan->indptr && plan->hub_rows,
+                    plan->rows && plan->indices && plan->indptr && plan->hub_rows &&
+                    plan->starts && plan->start_rank && plan->row_ids,
                 "hub plan does not belong to this CSR");
     a.indptr = IdxPtr{plan->indptr, 0};
     a.rows = plan->rows;
@@ -459,6 +461,9 @@ void run_fast(const ReduceWalk& rw, int kind, int red, const float* x, const int
     a.num_hubs = plan->num_hubs;
     a.hub_blocks = plan->num_blocks;
     a.hub_nnz = plan->hub_nnz;
+    a.starts = plan->starts;
+    a.start_rank = plan->start_rank;
+    a.row_ids = plan->row_ids;
   }
   const CarryLayout lay((walk.nnz + a.chunk - 1) / a.chunk, F);
   Scratch carry(rw.ws, lay.bytes, s);

@@ -416,6 +416,11 @@ struct FastArgs {
   int64_t hub_blocks;
   int64_t hub_nnz;      // positions of the virtual rows (the plan's first part)
   int64_t plan_wgs;     // workgroups remapped to their XCD's source block (a multiple of 8)
+  // the plan's row starts (DGLMIHubPlan.starts / start_rank / row_ids): the plan walk of
+  // k_chunk_reduce reads these instead of one row id per position
+  const uint32_t* starts;
+  const int32_t* start_rank;
+  const int32_t* row_ids;
 };
 int64_t fast_chunk_edges(int64_t nnz, int64_t F);
 int64_t fast_workspace_bytes(int64_t nnz, int64_t F);  // carries + counters (CarryLayout)
@@ -425,6 +430,9 @@ void launch_fast_reduce(int kind, int red, const FastArgs& a, hipStream_t s);  /
 // out_cols[p] = cols[p] | (col_deg(cols[p]) < thresh ? 1 << 31 : 0), col_deg from deg_indptr
 void launch_mark_cold(const int32_t* cols, int64_t nnz, IdxPtr deg_indptr, int32_t thresh,
                       int32_t* out_cols, hipStream_t s);
+// longest chunk of a hub plan's walk: the kernel keeps a chunk's words of the start bitmap
+// one per lane of a group, 16 lanes at the least (fast_chunk_edges gives 512 at the most)
+constexpr int64_t kPlanMaxChunk = 32 * 16;
 // row widths whose launch config has a marked variant (L >= 16 lanes, one float4 each)
 inline bool fast_marked_supported(int64_t F) { return F > 32 && F <= 256 && F % 4 == 0; }
 // tables smaller than this stay on the plain path (they fit the Infinity Cache)

@@ -7,6 +7,7 @@
 
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 namespace dglmi {
 namespace {
@@ -212,6 +213,9 @@ __device__ __forceinline__ float* row_dst(const FastArgs& a, int64_t r) {
   else return a.out + r * a.F;
 }
 
+__device__ __forceinline__ int popcount_bits(uint32_t v) { return __popc(v); }
+__device__ __forceinline__ int popcount_bits(uint64_t v) { return __popcll(v); }
+
 // PLAN: the first a.plan_wgs workgroups (a multiple of 8) walk the hub part, whose
 // positions are sorted by source block.  Workgroups b and b + 8 run on the same XCD, so
 // workgroup bid takes chunk group (bid % 8) * (plan_wgs / 8) + bid / 8: each XCD walks one
@@ -225,7 +229,15 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
   constexpr int B = (L > 16 ? L : 16) * ((VAR & 4) ? 2 : 1);  // positions staged per step
   constexpr int U = (NV == 1 ? 8 : (NV == 2 ? 4 : 2)) * ((VAR & 4) ? 2 : 1);
   static_assert(B % U == 0, "B must be a multiple of U");
-  __shared__ int32_t s_row[G][B];
+  static_assert(!PLAN || (B == L && KIND == FAST_COPY_COL), "the plan walk: one position and one window entry per lane");
+  // PLAN stages no row ids.  The chunk's words of the start bitmap (a.starts) are loaded
+  // once, one per lane (s_bits): a chunk of K <= kPlanMaxChunk = 32 * 16 positions begins on
+  // a word when K >= 32 and lies inside one when K < 32 (K is a power of two), so it has at
+  // most L words.  The ids of the rows that start in a batch are a window of a.row_ids,
+  // one entry per start (s_win).
+  __shared__ int32_t s_row[PLAN ? 1 : G][PLAN ? 1 : B];
+  __shared__ uint32_t s_bits[PLAN ? G : 1][PLAN ? L : 1];
+  __shared__ int32_t s_win[PLAN ? G : 1][PLAN ? B : 1];
   __shared__ int32_t s_col[G][B];
   __shared__ int64_t s_eid[needs_eid<KIND>() ? G : 1][needs_eid<KIND>() ? B : 1];
   // FAST_COL_MUL_POS: one scalar edge value per position (u_mul_e with one weight per
@@ -268,27 +280,73 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
   // batch's gathers are in flight, and written to LDS at the batch's start
   constexpr int SQ = B / L;  // positions each lane stages per batch
   constexpr bool kEid = needs_eid<KIND>();
-  int32_t nr[SQ], nc[SQ];
+  [[maybe_unused]] int32_t nr[SQ];
+  int32_t nc[SQ];
   [[maybe_unused]] int64_t ne[kEid ? SQ : 1];
   [[maybe_unused]] float nw[kScalarW ? SQ : 1];
-  auto fetch = [&](int64_t nb) {
-#pragma unroll
-    for (int i = 0; i < SQ; ++i) {
-      const int64_t p = nb + lane + i * L;
-      const bool ok = p < p1;
-      nr[i] = ok ? ld_stream<VAR>(a.rows + p) : INT_MAX;
-      nc[i] = ok ? ld_stream<VAR>(a.indices + p) : 0;
-      // identity edge ids (a position view's walk, a.eids null): no `data` stream
-      if constexpr (kEid) ne[kEid ? i : 0] = ok ? (a.eids ? ld_stream<VAR>(a.eids, p) : p) : 0;
-      if constexpr (kScalarW) nw[kScalarW ? i : 0] = ok ? ld_stream_f<VAR>(a.w + p) : 0.0f;
+  // PLAN: `bits` are the start flags of the batch last fetched (bit i: position nb + i,
+  // those at or past p1 cleared) and `win0` the index in a.row_ids of its first start, so
+  // a fetch knows its window without waiting for a load.  The chunk's first position
+  // starts no row here: cur and cont above hold its row.
+  using Bits = std::conditional_t<(B > 32), uint64_t, uint32_t>;
+  [[maybe_unused]] Bits bits = 0;
+  [[maybe_unused]] int64_t win0 = 0;
+  [[maybe_unused]] int32_t nwin = 0;
+  [[maybe_unused]] const int sh = static_cast<int>(p0 & 31);  // not 0 only when K < 32
+  [[maybe_unused]] auto batch_bits = [&](int64_t nb) -> Bits {
+    const int o = static_cast<int>(nb - p0) + sh;
+    const int n = p1 - nb < B ? static_cast<int>(p1 - nb) : B;
+    if constexpr (B > 32) {
+      const uint64_t v = ((static_cast<uint64_t>(s_bits[PLAN ? g : 0][PLAN ? (o >> 5) + 1 : 0]) << 32) |
+                          s_bits[PLAN ? g : 0][PLAN ? o >> 5 : 0]) >> (o & 31);
+      return n >= 64 ? v : v & ((uint64_t(1) << n) - 1);
+    } else {
+      const uint32_t v = s_bits[PLAN ? g : 0][PLAN ? o >> 5 : 0] >> (o & 31);
+      return n >= 32 ? v : v & ((1u << n) - 1u);
     }
   };
-  fetch(p0);
+  auto fetch = [&](int64_t nb, [[maybe_unused]] bool cols = true) {
+    if constexpr (PLAN) {
+      if (cols) nc[0] = nb + lane < p1 ? ld_stream<VAR>(a.indices + nb + lane) : 0;
+      win0 += popcount_bits(bits);
+      bits = batch_bits(nb);
+      if (nb == p0) bits &= ~Bits(1);
+      nwin = lane < popcount_bits(bits) ? a.row_ids[win0 + lane] : 0;
+    } else {
+#pragma unroll
+      for (int i = 0; i < SQ; ++i) {
+        const int64_t p = nb + lane + i * L;
+        const bool ok = p < p1;
+        nr[i] = ok ? ld_stream<VAR>(a.rows + p) : INT_MAX;
+        nc[i] = ok ? ld_stream<VAR>(a.indices + p) : 0;
+        // identity edge ids (a position view's walk, a.eids null): no `data` stream
+        if constexpr (kEid) ne[kEid ? i : 0] = ok ? (a.eids ? ld_stream<VAR>(a.eids, p) : p) : 0;
+        if constexpr (kScalarW) nw[kScalarW ? i : 0] = ok ? ld_stream_f<VAR>(a.w + p) : 0.0f;
+      }
+    }
+  };
+  if constexpr (PLAN) {
+    // the chunk's bitmap words, the rank of the first and the first batch's columns in
+    // flight together; then the first window, whose index needs the first word
+    const int64_t w0 = p0 >> 5;
+    const uint32_t word = (w0 + lane) * 32 < p1 ? a.starts[w0 + lane] : 0u;
+    const int32_t rank0 = a.start_rank[w0];
+    nc[0] = p0 + lane < p1 ? ld_stream<VAR>(a.indices + p0 + lane) : 0;
+    s_bits[PLAN ? g : 0][PLAN ? lane : 0] = word;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    win0 = rank0 + __popc(s_bits[PLAN ? g : 0][0] & ((2u << sh) - 1u));
+    fetch(p0, false);
+  } else {
+    fetch(p0);
+  }
   for (int64_t base = p0; base < p1; base += B) {
 #pragma unroll
     for (int i = 0; i < SQ; ++i) {
       const int q = lane + i * L;
-      s_row[g][q] = nr[i];
+      if constexpr (PLAN) s_win[PLAN ? g : 0][PLAN ? q : 0] = nwin;
+      else s_row[PLAN ? 0 : g][PLAN ? 0 : q] = nr[i];
       s_col[g][q] = nc[i];
       if constexpr (kEid) s_eid[kEid ? g : 0][q] = ne[kEid ? i : 0];
       if constexpr (kScalarW) s_w[kScalarW ? g : 0][kScalarW ? q : 0] = nw[kScalarW ? i : 0];
@@ -296,6 +354,9 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // PLAN: this batch's flags and its positions inside the chunk (fetch moves on)
+    [[maybe_unused]] const Bits cb = bits;
+    [[maybe_unused]] const int cn = p1 - base < B ? static_cast<int>(p1 - base) : B;
     if (base + B < p1) fetch(base + B);
     // the mul kinds load both operands in the gather loop and multiply in the
     // accumulation loop: a product inside the bounds-checked gather made the compiler
@@ -354,7 +415,9 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
       for (int u = 0; u < U; ++u) {
         const int32_t col = s_col[g][ub + u];
         const int64_t eid = needs_eid<KIND>() ? s_eid[needs_eid<KIND>() ? g : 0][ub + u] : 0;
-        const bool ok = s_row[g][ub + u] != INT_MAX;
+        [[maybe_unused]] int32_t srow = 0;  // (the tie kind's walk row; never a plan walk)
+        if constexpr (!PLAN) srow = s_row[PLAN ? 0 : g][PLAN ? 0 : ub + u];
+        const bool ok = PLAN ? ub + u < cn : srow != INT_MAX;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
           const int f4 = lane + v * L;
@@ -378,7 +441,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
             const float* px = a.x + static_cast<int64_t>(col & 0x7fffffff) * a.F + VW * f4;
             val[u][v] = (ok && f4 < F4) ? (nt ? vld_nt<VW>(px) : vld<VW>(px)) : I;
           } else {
-            val[u][v] = (ok && f4 < F4) ? edge_value<KIND, VW>(a, col, eid, f4, hsel[v], wn, s_row[g][ub + u]) : I;
+            val[u][v] = (ok && f4 < F4) ? edge_value<KIND, VW>(a, col, eid, f4, hsel[v], wn, srow) : I;
             // (mapped mul kinds: the product is already in val, except the staged
             // per-position weight)
             if constexpr (kScalarW) wsc[u][kMulScl ? v : 0] = s_w[kScalarW ? g : 0][kScalarW ? ub + u : 0];
@@ -390,9 +453,20 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int32_t r = s_row[g][ub + u];
-        if (r == INT_MAX) break;
-        if (r != cur) {
+        // PLAN: a set flag ends the row; the next one's id is the window entry of the
+        // flag's rank in the batch
+        int32_t r = 0;
+        bool flush;
+        if constexpr (PLAN) {
+          if (ub + u >= cn) break;
+          flush = (cb >> (ub + u)) & 1;
+        } else {
+          r = s_row[PLAN ? 0 : g][PLAN ? 0 : ub + u];
+          if (r == INT_MAX) break;
+          flush = r != cur;
+        }
+        if (flush) {
+          if constexpr (PLAN) r = s_win[PLAN ? g : 0][PLAN ? popcount_bits(cb & ((Bits(1) << (ub + u)) - 1)) : 0];
           // flush the finished row (empty rows in between: fill_empty_rows)
           float* dst = cont ? a.carry + chunk * a.F : row_dst<PLAN>(a, cur);
 #pragma unroll

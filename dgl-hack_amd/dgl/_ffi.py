@@ -68,6 +68,9 @@ class HubPlan(ctypes.Structure):
         ("marked", ctypes.c_void_p),
         ("indptr", ctypes.c_void_p),
         ("hub_rows", ctypes.c_void_p),
+        ("starts", ctypes.c_void_p),
+        ("start_rank", ctypes.c_void_p),
+        ("row_ids", ctypes.c_void_p),
     ]
 
 

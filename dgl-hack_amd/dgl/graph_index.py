@@ -112,10 +112,33 @@ def build_hub_plan(indptr, indices, rows, hub_degree, nb=8):
     del order, vrow, hub_pos, light_pos
     out_ptr = th.zeros(virt + num_rows + 1, dtype=th.int64, device=indptr.device)
     out_ptr[1:] = th.cumsum(th.bincount(plan_rows, minlength=virt + num_rows), 0)
-    return {"num_blocks": nb, "num_hubs": nh, "hub_nnz": n_he, "positions": positions,
+    plan = {"num_blocks": nb, "num_hubs": nh, "hub_nnz": n_he, "positions": positions,
             "rows": plan_rows.to(th.int32), "indices": indices[positions].contiguous(),
             "indptr": out_ptr.to(th.int32), "hub_rows": hub_rows.to(th.int32),
             "cuts": cuts}
+    plan.update(plan_row_starts(plan["rows"]))
+    return plan
+
+
+def plan_row_starts(rows):
+    """Where the rows of a walk start, for a kernel that does not read ``rows`` (one
+    row id per position): ``starts``, a bitmap of ceil(nnz / 32) words plus one zero word
+    of padding, bit ``p & 31`` of word ``p >> 5`` set when position p is the first of its
+    row (int32 tensors holding the uint32 bit patterns); ``start_rank``, per word the
+    number of set bits before it; ``row_ids``, the row of every start in walk order."""
+    nnz = int(rows.shape[0])
+    first = th.ones(nnz, dtype=th.bool, device=rows.device)
+    first[1:] = rows[1:] != rows[:-1]
+    at = th.nonzero(first).reshape(-1)
+    del first
+    words = (nnz + 31) // 32 + 1
+    bits = th.zeros(words, dtype=th.int64, device=rows.device)
+    # one bit per start, no two alike in a word: the sum is the bitwise or
+    bits.index_add_(0, at >> 5, th.ones_like(at) << (at & 31))
+    count = th.bincount(at >> 5, minlength=words)
+    return {"starts": th.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(th.int32),
+            "start_rank": (th.cumsum(count, 0) - count).to(th.int32),
+            "row_ids": rows[at].to(th.int32).contiguous()}
 
 
 class ImmutableGraphIndex:
@@ -274,10 +297,12 @@ class ImmutableGraphIndex:
         c = _ffi.HubPlan()
         c.num_blocks, c.num_hubs = p["num_blocks"], p["num_hubs"]
         c.hub_nnz, c.nnz = p["hub_nnz"], csr.nnz
-        keep = (p["rows"], p["indices"], marked, p["indptr"], p["hub_rows"])
+        keep = (p["rows"], p["indices"], marked, p["indptr"], p["hub_rows"],
+                p["starts"], p["start_rank"], p["row_ids"])
         c.rows, c.indices = keep[0].data_ptr(), keep[1].data_ptr()
         c.marked = marked.data_ptr() if marked is not None else None
         c.indptr, c.hub_rows = keep[3].data_ptr(), keep[4].data_ptr()
+        c.starts, c.start_rank, c.row_ids = (t.data_ptr() for t in keep[5:])
         c._keep = keep  # alive as long as the struct
         return c
 

@@ -162,6 +162,13 @@ typedef struct DGLMIHubPlan {
   const int32_t* marked;   /* the same with cold marks in bit 31 ({in,out}_gather_cols), or NULL */
   const int32_t* indptr;   /* num_blocks * num_hubs + num_rows + 1 */
   const int32_t* hub_rows; /* num_hubs, the CSR row of every hub, ascending */
+  /* Where the plan's rows start, which is all the walk needs of `rows` (one bit per
+   * position and one id per non-empty row instead of 4 bytes per position; together
+   * about nnz / 4 bytes + 4 bytes per non-empty plan row): */
+  const uint32_t* starts;    /* ceil(nnz / 32) words + one zero word: bit p & 31 of word p >> 5
+                              * is set when p == 0 or rows[p] != rows[p - 1] */
+  const int32_t* start_rank; /* per word of `starts`: the set bits before it */
+  const int32_t* row_ids;    /* rows[p] of every set bit, in order */
 } DGLMIHubPlan;
 
 /* A contiguous row-major fp32 device array (NDArray / DLTensor subset). */
