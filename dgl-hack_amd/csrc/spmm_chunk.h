@@ -173,6 +173,17 @@ __device__ __forceinline__ int64_t ld_stream(IdxPtr q, int64_t p) {
   }
   return ld_stream<VAR>(static_cast<const int32_t*>(q.p) + p);
 }
+// Two consecutive int32 by one 8-byte load; p need only be 4-byte aligned.
+typedef int32_t i32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int VAR>
+__device__ __forceinline__ void ld_stream2(const int32_t* p, int32_t& v0, int32_t& v1) {
+  const i32x2_a4* q = reinterpret_cast<const i32x2_a4*>(p);
+  i32x2_a4 v;
+  if constexpr (VAR & 1) v = __builtin_nontemporal_load(q);
+  else v = *q;
+  v0 = v.x;
+  v1 = v.y;
+}
 template <int VAR>
 __device__ __forceinline__ float ld_stream_f(const float* p) {
   if constexpr (VAR & 1) return __builtin_nontemporal_load(p);
@@ -186,9 +197,13 @@ __device__ __forceinline__ void st_out(float* p, V v) {
 
 // L lanes per group, NV VW-float slots per lane, U gathers in flight per lane-slot.
 // VAR (tuning variants): bit 0 non-temporal index/row stream loads, bit 1
-// non-temporal output stores, bit 2 twice the gathers in flight.  Default 3:
-// keeping the once-read CSR stream and the once-written output out of L2/MALL
-// leaves more room for re-read source rows (M1: 3.30 -> 3.25 ms; 4 and 7 spill).
+// non-temporal output stores, bit 2 twice the gathers in flight.  Default 3
+// (M1: 3.30 -> 3.25 ms; 4 and 7 spill).  The nt stores do not keep the once-written
+// output out of L2: an nt store, like a plain one, leaves its line in the XCD's L2;
+// only a write-through (sc1) store drops it.  That was measured on the
+// plan walk and left out: the re-read source rows gained nothing (reads
+// past L2 14.86 -> 14.91 GB), the reduce kernel lost 0.06 ms, and the fixup and the
+// merge, which read those rows next, lost 0.016 and 0.015 ms.
 // EPI: fused epilogue on every finished row, out = acc * row_mul[r] / row_div[r]
 // + bias + addend[r] (GraphConv's norm and bias, the mean reducer's division,
 // accumulation onto an earlier partial result) -- applied
@@ -226,15 +241,18 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
   static_assert(!PLAN || !EPI, "the plan variant has no epilogue");
   static_assert(L >= 1 && L <= 64, "a lane group must fit in one wavefront (fill_empty_rows)");
   constexpr int G = kBlock / L;           // groups per block
-  constexpr int B = (L > 16 ? L : 16) * ((VAR & 4) ? 2 : 1);  // positions staged per step
+  // positions staged per step; the plan walk's 16-lane group stages 32, a whole 128-byte
+  // line of the column stream per fetch (with 16 every line was fetched twice)
+  constexpr int B = (PLAN && L == 16) ? 32 : (L > 16 ? L : 16) * ((VAR & 4) ? 2 : 1);
   constexpr int U = (NV == 1 ? 8 : (NV == 2 ? 4 : 2)) * ((VAR & 4) ? 2 : 1);
   static_assert(B % U == 0, "B must be a multiple of U");
-  static_assert(!PLAN || (B == L && KIND == FAST_COPY_COL), "the plan walk: one position and one window entry per lane");
+  static_assert(!PLAN || ((B == L || (L == 16 && B == 32)) && KIND == FAST_COPY_COL),
+                "the plan walk: a batch's flags are one 32-bit word, or one position per lane");
   // PLAN stages no row ids.  The chunk's words of the start bitmap (a.starts) are loaded
   // once, one per lane (s_bits): a chunk of K <= kPlanMaxChunk = 32 * 16 positions begins on
   // a word when K >= 32 and lies inside one when K < 32 (K is a power of two), so it has at
   // most L words.  The ids of the rows that start in a batch are a window of a.row_ids,
-  // one entry per start (s_win).
+  // one entry per start (s_win: up to B of them).
   __shared__ int32_t s_row[PLAN ? 1 : G][PLAN ? 1 : B];
   __shared__ uint32_t s_bits[PLAN ? G : 1][PLAN ? L : 1];
   __shared__ int32_t s_win[PLAN ? G : 1][PLAN ? B : 1];
@@ -291,7 +309,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
   using Bits = std::conditional_t<(B > 32), uint64_t, uint32_t>;
   [[maybe_unused]] Bits bits = 0;
   [[maybe_unused]] int64_t win0 = 0;
-  [[maybe_unused]] int32_t nwin = 0;
+  [[maybe_unused]] int32_t nwin[SQ] = {};
   [[maybe_unused]] const int sh = static_cast<int>(p0 & 31);  // not 0 only when K < 32
   [[maybe_unused]] auto batch_bits = [&](int64_t nb) -> Bits {
     const int o = static_cast<int>(nb - p0) + sh;
@@ -305,13 +323,31 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
       return n >= 32 ? v : v & ((1u << n) - 1u);
     }
   };
+  // PLAN: a lane's SQ columns are consecutive positions, nb + SQ * lane + i.  SQ == 2 (the
+  // 16-lane group): one 8-byte load, so a group reads 128 contiguous bytes; the last
+  // position of an odd tail by a 4-byte load.  nb is even (a chunk starts on a multiple of
+  // K >= 8, a batch on a multiple of 32 after it).
+  [[maybe_unused]] auto plan_cols = [&](int64_t nb) {
+    if constexpr (SQ == 2) {
+      const int64_t p = nb + 2 * lane;
+      nc[0] = 0;
+      nc[SQ - 1] = 0;
+      if (p + 1 < p1) ld_stream2<VAR>(a.indices + p, nc[0], nc[SQ - 1]);
+      else if (p < p1) nc[0] = ld_stream<VAR>(a.indices + p);
+    } else {
+      nc[0] = nb + lane < p1 ? ld_stream<VAR>(a.indices + nb + lane) : 0;
+    }
+  };
   auto fetch = [&](int64_t nb, [[maybe_unused]] bool cols = true) {
     if constexpr (PLAN) {
-      if (cols) nc[0] = nb + lane < p1 ? ld_stream<VAR>(a.indices + nb + lane) : 0;
+      if (cols) plan_cols(nb);
       win0 += popcount_bits(bits);
       bits = batch_bits(nb);
       if (nb == p0) bits &= ~Bits(1);
-      nwin = lane < popcount_bits(bits) ? a.row_ids[win0 + lane] : 0;
+      // window entries lane, lane + L ..; nothing is loaded past the batch's starts
+      const int ns = popcount_bits(bits);
+#pragma unroll
+      for (int i = 0; i < SQ; ++i) nwin[i] = lane + i * L < ns ? a.row_ids[win0 + lane + i * L] : 0;
     } else {
 #pragma unroll
       for (int i = 0; i < SQ; ++i) {
@@ -331,7 +367,7 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
     const int64_t w0 = p0 >> 5;
     const uint32_t word = (w0 + lane) * 32 < p1 ? a.starts[w0 + lane] : 0u;
     const int32_t rank0 = a.start_rank[w0];
-    nc[0] = p0 + lane < p1 ? ld_stream<VAR>(a.indices + p0 + lane) : 0;
+    plan_cols(p0);
     s_bits[PLAN ? g : 0][PLAN ? lane : 0] = word;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -345,9 +381,9 @@ __global__ void __launch_bounds__(kBlock) k_chunk_reduce(FastArgs a, IdxPtr indp
 #pragma unroll
     for (int i = 0; i < SQ; ++i) {
       const int q = lane + i * L;
-      if constexpr (PLAN) s_win[PLAN ? g : 0][PLAN ? q : 0] = nwin;
+      if constexpr (PLAN) s_win[PLAN ? g : 0][PLAN ? q : 0] = nwin[i];
       else s_row[PLAN ? 0 : g][PLAN ? 0 : q] = nr[i];
-      s_col[g][q] = nc[i];
+      s_col[g][PLAN ? SQ * lane + i : q] = nc[i];
       if constexpr (kEid) s_eid[kEid ? g : 0][q] = ne[kEid ? i : 0];
       if constexpr (kScalarW) s_w[kScalarW ? g : 0][kScalarW ? q : 0] = nw[kScalarW ? i : 0];
     }
