@@ -2649,3 +2649,232 @@ int DGLMINbAccess(const DGLMIGraph* graph, const DGLMIArray* feat, const int32_t
 }
 
 }  // extern "C"
+
+// ---- segment kernels (kernels_segment.hip) -----------------------------------
+namespace {
+struct SegCall {
+  int64_t N, B, F;
+  int device;
+};
+// the segments, and the arrays of a call against them: `rows` arrays have num_rows rows,
+// `segs` arrays num_segments, all F = row_floats(first) floats a row
+SegCall seg_setup(const DGLMISegments* seg, std::initializer_list<const DGLMIArray*> rows,
+                  std::initializer_list<const DGLMIArray*> segs) {
+  DGLMI_CHECK(seg != nullptr && seg->offsets != nullptr, "null segments");
+  DGLMI_CHECK(seg->num_segments >= 0 && seg->num_rows >= 0, "negative segment or row count");
+  SegCall c{seg->num_rows, seg->num_segments, -1, 0};
+  auto one = [&](const DGLMIArray* a, int64_t n, const char* what) {
+    check_array(a, what);
+    DGLMI_CHECK(a->shape[0] == n, std::string(what) + ": expected " + std::to_string(n) +
+                                      " rows, got " + std::to_string(a->shape[0]));
+    const int64_t f = feat_numel(a);
+    if (c.F < 0) c.F = f;
+    DGLMI_CHECK(f == c.F, std::string(what) + ": feature size " + std::to_string(f) +
+                              " differs from " + std::to_string(c.F));
+    DGLMI_CHECK(aligned16(a->data), std::string(what) + " must be 16-byte aligned");
+  };
+  for (const DGLMIArray* a : rows) one(a, c.N, "a per-row array");
+  for (const DGLMIArray* a : segs) one(a, c.B, "a per-segment array");
+  DGLMI_CHECK(c.F >= 0, "no array");
+  DGLMI_CHECK(c.N < (int64_t(1) << 40) && c.F < (int64_t(1) << 20), "table too large");
+  hipPointerAttribute_t at;
+  check_hip(hipPointerGetAttributes(&at, seg->offsets), "segment offsets: not a device pointer");
+  c.device = at.device;
+  return c;
+}
+int64_t seg_carry_bytes(int64_t N, int64_t F) { return (seg_workspace_bytes(N, F) + 15) & ~int64_t(15); }
+int64_t seg_stat_bytes(int64_t B, int64_t F) { return (2 * B * F * 4 + 15) & ~int64_t(15); }
+// Scratch of a segment walk: its carries and counters, then (the softmax entries only) two
+// (B, F) statistics tables
+struct SegScratch {
+  Scratch ws;
+  float* stat0 = nullptr;
+  float* stat1 = nullptr;
+  SegScratch(const DGLMISegments* seg, const SegCall& c, bool stats, hipStream_t s)
+      : ws(Workspace{aligned16(seg->workspace) ? seg->workspace : nullptr, seg->workspace_bytes},
+           seg_carry_bytes(c.N, c.F) + (stats ? seg_stat_bytes(c.B, c.F) : 0), s) {
+    if (stats) {
+      stat0 = reinterpret_cast<float*>(static_cast<char*>(ws.ptr) + seg_carry_bytes(c.N, c.F));
+      stat1 = stat0 + c.B * c.F;
+    }
+  }
+  void point(dglmi::SegArgs& a, const SegCall& c) const {
+    a.chunk = seg_chunk_rows(c.F);
+    a.chunks = c.N > 0 ? (c.N + a.chunk - 1) / a.chunk : 1;
+    CarryLayout(a.chunks, seg_rec_floats(SEG_MAX, c.F)).point(a, ws.ptr);
+  }
+};
+dglmi::SegArgs seg_args(const DGLMISegments* seg, const SegCall& c) {
+  dglmi::SegArgs a{};
+  a.offsets = seg->offsets;
+  a.num_segments = c.B;
+  a.num_rows = c.N;
+  a.F = c.F;
+  return a;
+}
+dglmi::SegRowArgs seg_row_args(const DGLMISegments* seg, const SegCall& c) {
+  dglmi::SegRowArgs a{};
+  a.offsets = seg->offsets;
+  a.num_segments = c.B;
+  a.num_rows = c.N;
+  a.F = c.F;
+  return a;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t DGLMISegmentChunkRows(int64_t row_floats) {
+  return row_floats > 0 ? seg_chunk_rows(row_floats) : 0;
+}
+
+int64_t DGLMISegmentWorkspaceBytes(int64_t num_rows, int64_t num_segments, int64_t row_floats) {
+  if (num_rows < 0 || num_segments <= 0 || row_floats <= 0) return 0;
+  return seg_carry_bytes(num_rows, row_floats);
+}
+
+int64_t DGLMISegmentSoftmaxWorkspaceBytes(int64_t num_rows, int64_t num_segments,
+                                          int64_t row_floats) {
+  if (num_rows < 0 || num_segments <= 0 || row_floats <= 0) return 0;
+  return seg_carry_bytes(num_rows, row_floats) + seg_stat_bytes(num_segments, row_floats);
+}
+
+int DGLMISegmentReduce(const char* reducer, const DGLMISegments* seg, const DGLMIArray* feat,
+                       const DGLMIArray* mul, DGLMIArray* out, int64_t* arg, void* stream) {
+  API_BEGIN();
+  const int red = parse_reducer(reducer);
+  DGLMI_CHECK(red == RED_SUM || red == RED_MAX || red == RED_MIN,
+              "segment reduce: reducer must be sum, max or min");
+  const SegCall c = seg_setup(seg, {feat}, {out});
+  DGLMI_CHECK((arg != nullptr) == (red != RED_SUM), "arg goes with max / min and with them only");
+  int mode = 0;
+  if (mul != nullptr) {
+    check_array(mul, "mul");
+    int64_t n = 1;
+    for (int i = 0; i < mul->ndim; ++i) n *= mul->shape[i];
+    DGLMI_CHECK(mul->shape[0] == c.N && (n == c.N || n == c.N * c.F),
+                "mul must have one scalar per row or feat's shape");
+    mode = (n == c.N * c.F && c.F != 1) ? 2 : 1;
+    // per-row scalars are read one float at a time; an elementwise mul like feat
+    DGLMI_CHECK(mode == 1 || aligned16(mul->data), "an elementwise mul must be 16-byte aligned");
+  }
+  if (c.B == 0 || c.F == 0) return 0;
+  DeviceGuard guard(c.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SegScratch sc(seg, c, false, s);
+  dglmi::SegArgs a = seg_args(seg, c);
+  sc.point(a, c);
+  a.x = feat->data;
+  a.w = mode == 1 ? mul->data : nullptr;
+  a.y = mode == 2 ? mul->data : nullptr;
+  a.out = out->data;
+  a.arg = arg;
+  launch_seg_reduce(red == RED_SUM ? SEG_SUM : (red == RED_MAX ? SEG_MAX : SEG_MIN), mode, a, s);
+  check_hip(hipGetLastError(), "segment reduce launch");
+  API_END();
+}
+
+int DGLMISegmentBroadcast(const DGLMISegments* seg, const DGLMIArray* v, const float* row_scale,
+                          int divide_by_length, DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  const SegCall c = seg_setup(seg, {out}, {v});
+  if (c.N == 0 || c.F == 0) return 0;
+  DGLMI_CHECK(c.B > 0, "rows without segments");
+  DeviceGuard guard(c.device);
+  dglmi::SegRowArgs a = seg_row_args(seg, c);
+  a.v = v->data;
+  a.w = row_scale;
+  a.divide = divide_by_length;
+  a.out = out->data;
+  launch_seg_rows(0, a, static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "segment broadcast launch");
+  API_END();
+}
+
+int DGLMISegmentRowDot(const DGLMISegments* seg, const DGLMIArray* x, const DGLMIArray* v,
+                       float* out, void* stream) {
+  API_BEGIN();
+  const SegCall c = seg_setup(seg, {x}, {v});
+  if (c.N == 0) return 0;
+  DGLMI_CHECK(out != nullptr, "null out");
+  DGLMI_CHECK(c.B > 0, "rows without segments");
+  DeviceGuard guard(c.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (c.F == 0) {
+    launch_fill(out, c.N, 0.0f, s);
+  } else {
+    dglmi::SegRowArgs a = seg_row_args(seg, c);
+    a.x = x->data;
+    a.v = v->data;
+    a.out = out;
+    launch_seg_rowdot(a, s);
+  }
+  check_hip(hipGetLastError(), "segment rowdot launch");
+  API_END();
+}
+
+int DGLMISegmentSoftmaxForward(const DGLMISegments* seg, const DGLMIArray* logits,
+                               DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  const SegCall c = seg_setup(seg, {logits, out}, {});
+  if (c.N == 0 || c.F == 0) return 0;
+  DGLMI_CHECK(c.B > 0, "rows without segments");
+  DeviceGuard guard(c.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SegScratch sc(seg, c, true, s);
+  dglmi::SegArgs a = seg_args(seg, c);
+  sc.point(a, c);
+  a.x = logits->data;
+  a.out = sc.stat0;
+  a.out2 = sc.stat1;
+  launch_seg_reduce(SEG_STATS, 0, a, s);
+  dglmi::SegRowArgs r = seg_row_args(seg, c);
+  r.x = logits->data;
+  r.v = sc.stat0;
+  r.v2 = sc.stat1;
+  r.out = out->data;
+  launch_seg_rows(1, r, s);
+  check_hip(hipGetLastError(), "segment softmax forward launch");
+  API_END();
+}
+
+int DGLMISegmentSoftmaxBackward(const DGLMISegments* seg, const DGLMIArray* out,
+                                const DGLMIArray* grad_out, DGLMIArray* grad_logits,
+                                void* stream) {
+  API_BEGIN();
+  const SegCall c = seg_setup(seg, {out, grad_out, grad_logits}, {});
+  if (c.N == 0 || c.F == 0) return 0;
+  DGLMI_CHECK(c.B > 0, "rows without segments");
+  DeviceGuard guard(c.device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SegScratch sc(seg, c, true, s);
+  dglmi::SegArgs a = seg_args(seg, c);
+  sc.point(a, c);
+  a.x = out->data;
+  a.y = grad_out->data;
+  a.out = sc.stat0;
+  launch_seg_reduce(SEG_SUM, 2, a, s);
+  dglmi::SegRowArgs r = seg_row_args(seg, c);
+  r.x = out->data;
+  r.y = grad_out->data;
+  r.v = sc.stat0;
+  r.out = grad_logits->data;
+  launch_seg_rows(2, r, s);
+  check_hip(hipGetLastError(), "segment softmax backward launch");
+  API_END();
+}
+
+int DGLMISegmentScatterArg(const DGLMISegments* seg, const int64_t* arg,
+                           const DGLMIArray* grad_out, DGLMIArray* grad_feat, void* stream) {
+  API_BEGIN();
+  const SegCall c = seg_setup(seg, {grad_feat}, {grad_out});
+  if (c.B == 0 || c.F == 0 || c.N == 0) return 0;
+  DGLMI_CHECK(arg != nullptr, "null arg");
+  DeviceGuard guard(c.device);
+  launch_seg_scatter_arg(arg, grad_out->data, c.B, c.F, c.N, grad_feat->data,
+                         static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "segment scatter launch");
+  API_END();
+}
+
+}  // extern "C"

@@ -199,6 +199,42 @@ __device__ __forceinline__ FixupRole fixup_role(const Args& a, IP indptr, int64_
   return w;
 }
 
+// The segment holding row i of a segment walk (kernels_segment.hip): the largest s in
+// [lo, hi] with offsets[s] <= i, so empty segments that start at i are passed over
+// (offsets non-decreasing, offsets[lo] <= i).
+__device__ __forceinline__ int64_t seg_of_row(const int64_t* offsets, int64_t lo, int64_t hi,
+                                              int64_t i) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (offsets[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// fixup_role for a segment walk: rows are walked in position order, `chunk` rows per
+// chunk, and no row-of-position stream exists, so the row cut at the chunk's start is
+// found by binary search in a.offsets (num_segments + 1 values).  The rest is
+// fixup_role's: the same roles, the same counters.
+template <typename Args>
+__device__ __forceinline__ FixupRole fixup_role_segments(const Args& a, int64_t chunk) {
+  FixupRole w{};
+  w.chunk = chunk;
+  const int64_t K = a.chunk;
+  const int64_t p0 = chunk * K;
+  if (chunk == 0 || p0 >= a.num_rows) return w;
+  w.r = seg_of_row(a.offsets, 0, a.num_segments - 1, p0);
+  const int64_t start = a.offsets[w.r];
+  if (start >= p0) return w;  // not a continuation
+  w.first = start / K + 1;
+  w.last = (a.offsets[w.r + 1] - 1) / K;
+  w.nseg = a.seg_cnt != nullptr ? (w.last - w.first + kFixSeg) / kFixSeg : 1;
+  if (w.nseg == 1 ? chunk != w.first : (chunk - w.first) % kFixSeg != 0) return w;
+  w.cend = w.nseg == 1 ? w.last : (chunk + kFixSeg - 1 < w.last ? chunk + kFixSeg - 1 : w.last);
+  w.work = true;
+  return w;
+}
+
 // The two phases.  fold(false, c0, c1, 1): fold carry records c0..c1 in chunk order
 // and store the partial in record c0.  fold(true, c0, c1, step): fold the row head and
 // records c0, c0 + step, .. c1 in that order and store the finished row.  Whether a
@@ -689,5 +725,50 @@ int64_t gemm_splits(int64_t M, int64_t N, int64_t K);
 void launch_gemm(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs,
                  int64_t b_cs, float* C, int64_t M, int64_t N, int64_t K, int64_t splits,
                  float* partials, hipStream_t s);
+
+// Segment kernels (kernels_segment.hip): rows 0..num_rows-1 of an (N, F) table in
+// position order, segment b = rows offsets[b] .. offsets[b + 1] (a batch of graphs'
+// nodes or edges).  No gather, no index stream.
+enum SegRed : int { SEG_SUM = 0, SEG_MAX = 1, SEG_MIN = 2, SEG_STATS = 3 };
+struct SegArgs {
+  const int64_t* offsets;  // num_segments + 1, device
+  int64_t num_segments;
+  int64_t num_rows;
+  int64_t F;
+  const float* x;          // (N, F)
+  const float* w;          // optional per-row scalar (N)
+  const float* y;          // optional elementwise operand (N, F)
+  float* out;              // (B, F): sum / max / min, or the softmax's running max
+  float* out2;             // (B, F): the softmax's sum of exp(s - max)
+  int64_t* arg;            // (B, F): max / min, lowest row that attains the value
+  float* carry;            // chunks records (CarryLayout), see seg_rec_floats
+  int32_t* seg_cnt;
+  int64_t chunk;           // rows per chunk (seg_chunk_rows)
+  int64_t chunks;
+};
+int64_t seg_chunk_rows(int64_t F);
+int64_t seg_rec_floats(int red, int64_t F);
+int64_t seg_workspace_bytes(int64_t num_rows, int64_t F);  // carries + counters
+// mul: 0 none, 1 a.w, 2 a.y
+void launch_seg_reduce(int red, int mul, const SegArgs& a, hipStream_t s);
+// Per-row kernels over the same walk.  mode 0: out[i] = v[seg] (/ max(len, 1)) (* w[i]);
+// 1: out[i] = exp(x[i] - v[seg]) / v2[seg]; 2: out[i] = x[i] y[i] - x[i] v[seg]
+struct SegRowArgs {
+  const int64_t* offsets;
+  int64_t num_segments, num_rows, F;
+  const float* v;
+  const float* v2;
+  const float* x;
+  const float* y;
+  const float* w;
+  int divide;
+  float* out;
+};
+void launch_seg_rows(int mode, const SegRowArgs& a, hipStream_t s);
+// out[i] = sum_f x[i, f] v[seg(i), f]
+void launch_seg_rowdot(const SegRowArgs& a, hipStream_t s);
+// out[arg[b, f], f] = gy[b, f] where arg >= 0 (out zero-filled by the caller)
+void launch_seg_scatter_arg(const int64_t* arg, const float* gy, int64_t B, int64_t F,
+                            int64_t num_rows, float* out, hipStream_t s);
 
 }  // namespace dglmi

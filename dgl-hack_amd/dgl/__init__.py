@@ -11,7 +11,11 @@ from ._ffi import DGLError  # noqa: F401
 from . import function  # noqa: F401
 from . import backend  # noqa: F401
 from . import kernel  # noqa: F401
-from .graph import DGLGraph, ALL  # noqa: F401
+from .graph import DGLGraph, ALL, batch, unbatch  # noqa: F401
+from . import readout  # noqa: F401
+from .readout import (sum_nodes, sum_edges, mean_nodes, mean_edges, max_nodes,  # noqa: F401
+                      max_edges, softmax_nodes, softmax_edges, broadcast_nodes,
+                      broadcast_edges, topk_nodes, topk_edges)
 from .graph_index import GraphIndex  # noqa: F401
 from .heterograph import (DGLHeteroGraph, heterograph, graph, bipartite,  # noqa: F401
                           hetero_from_relations)

@@ -115,6 +115,17 @@ class DropoutDraw(ctypes.Structure):
     ]
 
 
+class Segments(ctypes.Structure):
+    """DGLMISegments (include/dglmi.h): the row segments of a batch."""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p),
+        ("num_segments", ctypes.c_int64),
+        ("num_rows", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 class Array(ctypes.Structure):
     _fields_ = [
         ("data", ctypes.c_void_p),
@@ -366,6 +377,27 @@ _SIGS = {
         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),
     "DGLMIStreamCopy": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "DGLMISegmentWorkspaceBytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "DGLMISegmentSoftmaxWorkspaceBytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64,
+                                                          ctypes.c_int64]),
+    "DGLMISegmentChunkRows": (ctypes.c_int64, [ctypes.c_int64]),
+    "DGLMISegmentReduce": (ctypes.c_int, [
+        ctypes.c_char_p, ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMISegmentBroadcast": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.c_void_p, ctypes.c_int,
+        ctypes.POINTER(Array), ctypes.c_void_p]),
+    "DGLMISegmentRowDot": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.c_void_p,
+        ctypes.c_void_p]),
+    "DGLMISegmentSoftmaxForward": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.c_void_p]),
+    "DGLMISegmentSoftmaxBackward": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.c_void_p]),
+    "DGLMISegmentScatterArg": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.c_void_p, ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -21,6 +21,7 @@ import os
 import weakref
 
 import torch as th
+from torch.autograd.function import once_differentiable
 
 from . import kernel as K
 from ._ffi import DGLError
@@ -859,3 +860,202 @@ def rgcn_layer1(graph, x, weight, norm, etypes=None):
     R, fi, fo = weight.shape
     y = project(x, weight.permute(1, 0, 2).reshape(fi, R * fo))  # (N, R * F_out)
     return _typed_aggregate(graph, R, y.view(x.shape[0] * R, fo), norm, etypes, node_major=True)
+
+
+# ---- segment operators (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -----------------
+def _flat2(t):
+    """``t`` as (rows, everything else); reshape(rows, -1) cannot infer -1 when rows == 0."""
+    width = 1
+    for d in t.shape[1:]:
+        width *= d
+    return t.reshape(t.shape[0], width)
+
+
+def _seg_rows(seg, t, name):
+    """``t`` as a contiguous, 16-byte aligned (N, F) view for the segment kernels."""
+    if t.dim() == 0 or t.shape[0] != seg.num_rows:
+        raise DGLError("Expected %s with first dimension %d, got shape %s"
+                       % (name, seg.num_rows, tuple(t.shape)))
+    return K._aligned(_flat2(t))
+
+
+def _seg_lengths(seg):
+    return (seg.offsets[1:] - seg.offsets[:-1]).clamp(min=1).to(th.float32).unsqueeze(1)
+
+
+class _SegmentReduce(th.autograd.Function):
+    """out[b] = reduce over segment b of feat (* weight): sum, mean (the sum over max(len,
+    1)), max, min.  weight: one scalar per row, or feat's shape (sum / mean only)."""
+
+    @staticmethod
+    def forward(ctx, reducer, seg, feat, weight):
+        x = _seg_rows(seg, feat, "feat")
+        f = x.shape[1]
+        red = "sum" if reducer == "mean" else reducer
+        if red not in ("sum", "max", "min"):
+            raise DGLError("Unsupported segment reducer: %s" % reducer)
+        w = None
+        if weight is not None:
+            if red != "sum":
+                raise DGLError("segment %s takes no weight" % reducer)
+            if weight.shape[0] != seg.num_rows or weight.numel() not in (seg.num_rows, x.numel()):
+                raise DGLError("weight must have one scalar per row or feat's shape, got %s for "
+                               "feat %s" % (tuple(weight.shape), tuple(feat.shape)))
+            w = K._aligned(_flat2(weight))
+        out = x.new_empty((seg.num_segments, f))
+        arg = None
+        if red != "sum":
+            arg = th.empty((seg.num_segments, f), dtype=th.int64, device=x.device)
+        K.segment_reduce(red, seg, x, w, out, arg)
+        if reducer == "mean":
+            out = out / _seg_lengths(seg)
+        ctx.seg, ctx.reducer, ctx.shape = seg, reducer, tuple(feat.shape)
+        ctx.wshape = None if weight is None else tuple(weight.shape)
+        ctx.save_for_backward(x if w is not None and ctx.needs_input_grad[3] else None, w, arg)
+        return out.reshape((seg.num_segments,) + tuple(feat.shape[1:]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        seg = ctx.seg
+        x, w, arg = ctx.saved_tensors
+        gy = K._aligned(_flat2(gy))
+        f = gy.shape[1]
+        gx = gw = None
+        if ctx.reducer in ("max", "min"):
+            if ctx.needs_input_grad[2]:
+                gx = gy.new_zeros((seg.num_rows, f))
+                K.segment_scatter_arg(seg, arg, gy, gx)
+            return None, None, None if gx is None else gx.reshape(ctx.shape), None
+        mean = ctx.reducer == "mean"
+        scalar = w is not None and w.shape[1] == 1
+        if ctx.needs_input_grad[2]:
+            gx = gy.new_empty((seg.num_rows, f))
+            K.segment_broadcast(seg, gy, gx, row_scale=w.reshape(-1) if scalar else None,
+                                divide_by_length=mean)
+            if w is not None and not scalar:
+                gx = gx * w
+            gx = gx.reshape(ctx.shape)
+        if w is not None and ctx.needs_input_grad[3]:
+            g = gy / _seg_lengths(seg) if mean else gy
+            if scalar:
+                gw = K.segment_rowdot(seg, x, K._aligned(g), gy.new_empty(seg.num_rows))
+            else:
+                gw = K.segment_broadcast(seg, K._aligned(g), gy.new_empty((seg.num_rows, f))) * x
+            gw = gw.reshape(ctx.wshape)
+        return None, None, gx, gw
+
+
+def segment_reduce(reducer, seg, feat, weight=None):
+    """Reduce the rows of ``feat`` (N, ...) over the segments ``seg`` (kernel.Segments) to
+    (B, ...): "sum", "mean", "max" or "min"; ``weight`` (N,) / (N, 1) multiplies each row,
+    a weight of feat's shape each element, before a sum or mean."""
+    return _SegmentReduce.apply(reducer, seg, feat, weight)
+
+
+class _SegmentBroadcast(th.autograd.Function):
+    """out[i] = v[segment of i] (* row_scale[i]): every segment's row to its rows."""
+
+    @staticmethod
+    def forward(ctx, seg, v, row_scale):
+        if v.dim() == 0 or v.shape[0] != seg.num_segments:
+            raise DGLError("Expected a tensor with first dimension %d (the batch size), got "
+                           "shape %s" % (seg.num_segments, tuple(v.shape)))
+        v2 = K._aligned(_flat2(v))
+        s = None
+        if row_scale is not None:
+            if row_scale.numel() != seg.num_rows:
+                raise DGLError("row_scale must have one value per row")
+            s = row_scale.reshape(-1).contiguous()
+        out = v2.new_empty((seg.num_rows, v2.shape[1]))
+        K.segment_broadcast(seg, v2, out, row_scale=s)
+        ctx.seg, ctx.vshape = seg, tuple(v.shape)
+        ctx.sshape = None if row_scale is None else tuple(row_scale.shape)
+        ctx.save_for_backward(v2 if s is not None and ctx.needs_input_grad[2] else None, s)
+        return out.reshape((seg.num_rows,) + tuple(v.shape[1:]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        seg = ctx.seg
+        v2, s = ctx.saved_tensors
+        g = K._aligned(_flat2(g))
+        gv = gs = None
+        if ctx.needs_input_grad[1]:
+            gv = g.new_empty((seg.num_segments, g.shape[1]))
+            K.segment_reduce("sum", seg, g, None if s is None else s.reshape(-1, 1), gv)
+            gv = gv.reshape(ctx.vshape)
+        if s is not None and ctx.needs_input_grad[2]:
+            gs = K.segment_rowdot(seg, g, v2, g.new_empty(seg.num_rows)).reshape(ctx.sshape)
+        return None, gv, gs
+
+
+def segment_broadcast(seg, v, row_scale=None):
+    """(N, ...) from (B, ...): row i takes ``v`` of its segment, times ``row_scale[i]``."""
+    return _SegmentBroadcast.apply(seg, v, row_scale)
+
+
+class _SegmentRowDot(th.autograd.Function):
+    """out[i] = <x[i], v[segment of i]> without the (N, F) product."""
+
+    @staticmethod
+    def forward(ctx, seg, x, v):
+        x2 = _seg_rows(seg, x, "x")
+        if v.dim() == 0 or v.shape[0] != seg.num_segments:
+            raise DGLError("Expected a tensor with first dimension %d (the batch size), got "
+                           "shape %s" % (seg.num_segments, tuple(v.shape)))
+        v2 = K._aligned(_flat2(v))
+        out = K.segment_rowdot(seg, x2, v2, x2.new_empty(seg.num_rows))
+        ctx.seg, ctx.xshape, ctx.vshape = seg, tuple(x.shape), tuple(v.shape)
+        ctx.save_for_backward(x2 if ctx.needs_input_grad[2] else None,
+                              v2 if ctx.needs_input_grad[1] else None)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        seg = ctx.seg
+        x2, v2 = ctx.saved_tensors
+        g = g.reshape(-1).contiguous()
+        gx = gv = None
+        if ctx.needs_input_grad[1]:
+            gx = g.new_empty((seg.num_rows, v2.shape[1]))
+            K.segment_broadcast(seg, v2, gx, row_scale=g)
+            gx = gx.reshape(ctx.xshape)
+        if ctx.needs_input_grad[2]:
+            gv = g.new_empty((seg.num_segments, x2.shape[1]))
+            K.segment_reduce("sum", seg, x2, g.reshape(-1, 1), gv)
+            gv = gv.reshape(ctx.vshape)
+        return None, gx, gv
+
+
+def segment_rowdot(seg, x, v):
+    """(N,): the dot product of every row of ``x`` (N, F) with its segment's row of ``v``
+    (B, F)."""
+    return _SegmentRowDot.apply(seg, x, v)
+
+
+class _SegmentSoftmax(th.autograd.Function):
+    """Softmax of every column of ``logits`` (N, ...) over each segment."""
+
+    @staticmethod
+    def forward(ctx, seg, logits):
+        s = _seg_rows(seg, logits, "logits")
+        out = K.segment_softmax_forward(seg, s, th.empty_like(s))
+        ctx.seg = seg
+        ctx.save_for_backward(out)
+        return out.reshape(logits.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (out,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        g2 = K._aligned(g.reshape(out.shape))
+        gs = K.segment_softmax_backward(ctx.seg, out, g2, th.empty_like(out))
+        return None, gs.reshape(g.shape)
+
+
+def segment_softmax(seg, logits):
+    return _SegmentSoftmax.apply(seg, logits)

@@ -222,7 +222,7 @@ class DGLGraph(object):
     """Base graph class (``python/dgl/graph.py:DGLGraph``, homogeneous)."""
 
     def __init__(self, graph_data=None, node_frame=None, edge_frame=None, multigraph=None,
-                 readonly=False):
+                 readonly=False, batch_num_nodes=None, batch_num_edges=None):
         self._graph = GraphIndex(0)
         self._readonly = False
         self._node_frame = Frame(self.number_of_nodes)
@@ -236,6 +236,10 @@ class DGLGraph(object):
             for k, v in edge_frame.items():
                 self._edge_frame[k] = v
         self._readonly = bool(readonly)
+        # nodes / edges of each graph of a batch (graph.py:1032-1033); None: a batch of one
+        self._batch_num_nodes = None if batch_num_nodes is None else [int(n) for n in batch_num_nodes]
+        self._batch_num_edges = None if batch_num_edges is None else [int(n) for n in batch_num_edges]
+        self._segment_cache = {}
 
     def _init_from(self, data):
         if isinstance(data, GraphIndex):
@@ -314,8 +318,72 @@ class DGLGraph(object):
         if self._readonly:
             raise DGLError("Mutation is not allowed in read-only graph.")
 
+    def _drop_batch(self):
+        """A mutation makes the graph a batch of one (graph.py:805-819, 1651-1652)."""
+        if self.batch_size > 1:
+            import warnings
+            warnings.warn("The graph has batch_size > 1, and mutation would break"
+                          " batching related properties, call `flatten` to remove"
+                          " batching information of the graph.")
+        self._batch_num_nodes = None
+        self._batch_num_edges = None
+        self._segment_cache = {}
+
+    # ---- batching (graph.py:2184-2215) ---------------------------------------------
+    @property
+    def batch_size(self):
+        """Number of graphs in this batch; 1 for a graph that is no batch."""
+        bnn = getattr(self, "_batch_num_nodes", None)
+        return 1 if bnn is None else len(bnn)
+
+    @property
+    def batch_num_nodes(self):
+        """Number of nodes of each graph in this batch."""
+        bnn = getattr(self, "_batch_num_nodes", None)
+        return [self.number_of_nodes()] if bnn is None else bnn
+
+    @property
+    def batch_num_edges(self):
+        """Number of edges of each graph in this batch."""
+        bne = getattr(self, "_batch_num_edges", None)
+        return [self.number_of_edges()] if bne is None else bne
+
+    def flatten(self):
+        """Forget the batch: the graph becomes a batch of one (graph.py:1639-1652)."""
+        self._batch_num_nodes = None
+        self._batch_num_edges = None
+        self._segment_cache = {}
+
+    def _segments(self, kind, device):
+        """The device int64 offsets tensor (batch_size + 1 values) of the batch's node
+        (``kind`` "nodes") or edge ("edges") segments, built once per graph and device from
+        the Python lists, so a readout call does no host synchronisation.  The cache is
+        shared with ``local_var`` / ``to`` copies and is left out when the graph is
+        pickled (``__getstate__``)."""
+        cache = self.__dict__.setdefault("_segment_cache", {})
+        device = th.device(device)
+        nums = self.batch_num_nodes if kind == "nodes" else self.batch_num_edges
+        total = self.number_of_nodes() if kind == "nodes" else self.number_of_edges()
+        key = (kind, str(device))
+        hit = cache.get(key)
+        if hit is None or hit[0] != (len(nums), total):
+            off = np.zeros(len(nums) + 1, np.int64)
+            np.cumsum(np.asarray(nums, np.int64), out=off[1:])
+            if int(off[-1]) != total:
+                raise DGLError("batch_num_%s sums to %d, the graph has %d" % (kind, off[-1], total))
+            hit = ((len(nums), total), th.from_numpy(off).to(device))
+            cache[key] = hit
+        return hit[1]
+
+    def __getstate__(self):
+        # device tensors of the segment cache do not travel (DataLoader workers): rebuilt on use
+        state = dict(self.__dict__)
+        state["_segment_cache"] = {}
+        return state
+
     def add_nodes(self, num, data=None):
         self._check_mutable()
+        self._drop_batch()
         old = self.number_of_nodes()
         self._graph.add_nodes(num)
         self._extend_frame(self._node_frame, old, int(num), data)
@@ -325,6 +393,7 @@ class DGLGraph(object):
 
     def add_edges(self, u, v, data=None):
         self._check_mutable()
+        self._drop_batch()
         old = self.number_of_edges()
         self._graph.add_edges(_to_index_array(u, "u"), _to_index_array(v, "v"))
         self._extend_frame(self._edge_frame, old, self.number_of_edges() - old, data)
@@ -344,6 +413,7 @@ class DGLGraph(object):
     def add_edges_with_type(self, u, v, etypes, data=None):
         """Add typed edges (the hack's graph.py:1229); types feed R-GCN kernels."""
         self._check_mutable()
+        self._drop_batch()
         old = self.number_of_edges()
         self._graph.add_edges_with_type(_to_index_array(u, "u"), _to_index_array(v, "v"),
                                         _to_index_array(etypes, "etypes"))
@@ -502,6 +572,7 @@ class DGLGraph(object):
 
     def clear(self):
         """Remove every node, edge, feature and pending message (graph.py:1190)."""
+        self._drop_batch()
         self._graph = GraphIndex(0)
         self._node_frame = Frame(self.number_of_nodes, None, self._node_frame._inits)
         self._edge_frame = Frame(self.number_of_edges, None, self._edge_frame._inits)
@@ -611,6 +682,9 @@ class DGLGraph(object):
         g._readonly = self._readonly
         g._node_frame = Frame(g.number_of_nodes, self._node_frame._cols, self._node_frame._inits)
         g._edge_frame = Frame(g.number_of_edges, self._edge_frame._cols, self._edge_frame._inits)
+        g._batch_num_nodes = getattr(self, "_batch_num_nodes", None)
+        g._batch_num_edges = getattr(self, "_batch_num_edges", None)
+        g._segment_cache = self.__dict__.setdefault("_segment_cache", {})
         for attr in ("_message_func", "_reduce_func", "_apply_node_func", "_apply_edge_func"):
             if hasattr(self, attr):
                 setattr(g, attr, getattr(self, attr))
@@ -1112,3 +1186,91 @@ class _PartialIndex(GraphIndex):
             (op, oi, od), (ip, ii, idd) = super().host_csr()
             self._host_csr = ((op, oi, self._parent[od]), (ip, ii, self._parent[idd]))
         return self._host_csr
+
+
+def batch(graph_list, node_attrs=ALL, edge_attrs=ALL):
+    """Batch a list of graphs into one graph, their disjoint union in list order
+    (``graph.py:4029-4239``).  Graph i's nodes and edges get ids offset by the nodes and
+    edges of the graphs before it, the frames are concatenated, and
+    ``batch_num_nodes`` / ``batch_num_edges`` keep each graph's counts; batching graphs
+    that are batches themselves flattens them.  ``node_attrs`` / ``edge_attrs``: ALL
+    (every graph with nodes / edges must carry the same fields), None, a field name or an
+    iterable of names."""
+    graph_list = list(graph_list)
+    if len(graph_list) == 1:
+        return graph_list[0]
+
+    def _init_attrs(attrs, mode):
+        if mode == "node":
+            nitems = [g.number_of_nodes() for g in graph_list]
+            have = [set(g._node_frame.keys()) for g in graph_list]
+        else:
+            nitems = [g.number_of_edges() for g in graph_list]
+            have = [set(g._edge_frame.keys()) for g in graph_list]
+        if attrs is None:
+            return []
+        if is_all(attrs):
+            attrs = set()
+            for i, (n, a) in enumerate(zip(nitems, have)):
+                if n > 0 and len(a) > 0:
+                    attrs, ref_g_index = a, i
+                    break
+            if len(attrs) > 0:
+                for i, (n, a) in enumerate(zip(nitems, have)):
+                    if a != attrs and n > 0:
+                        raise ValueError("Expect graph {0} and {1} to have the same {2} "
+                                         "attributes when {2}_attrs=ALL, got {3} and {4}."
+                                         .format(ref_g_index, i, mode, attrs, a))
+            return attrs
+        if isinstance(attrs, str):
+            return [attrs]
+        if hasattr(attrs, "__iter__"):
+            return list(attrs)
+        raise ValueError("Expected {} attrs to be of type None str or Iterable, "
+                         "got type {}".format(mode, type(attrs)))
+
+    node_attrs = _init_attrs(node_attrs, "node")
+    edge_attrs = _init_attrs(edge_attrs, "edge")
+
+    index = GraphIndex(0)
+    srcs, dsts, off = [], [], 0
+    for g in graph_list:
+        s, d, _ = g._graph.edges()
+        srcs.append(np.asarray(s, np.int64) + off)
+        dsts.append(np.asarray(d, np.int64) + off)
+        off += g.number_of_nodes()
+    index.add_nodes(off)
+    if srcs:
+        index.add_edges(np.concatenate(srcs), np.concatenate(dsts))
+    node_frame = {k: th.cat([g._node_frame[k] for g in graph_list if g.number_of_nodes() > 0], 0)
+                  for k in node_attrs}
+    edge_frame = {k: th.cat([g._edge_frame[k] for g in graph_list if g.number_of_edges() > 0], 0)
+                  for k in edge_attrs}
+    bnn, bne = [], []
+    for g in graph_list:
+        bnn += list(g.batch_num_nodes)
+        bne += list(g.batch_num_edges)
+    return DGLGraph(index, node_frame, edge_frame, batch_num_nodes=bnn, batch_num_edges=bne)
+
+
+def unbatch(graph):
+    """The graphs of a batch (``graph.py:4241-4288``): node and edge ids back to each
+    graph's own, every frame column split by ``batch_num_nodes`` / ``batch_num_edges``."""
+    if graph.batch_size == 1:
+        return [graph]
+    bnn, bne = graph.batch_num_nodes, graph.batch_num_edges
+    src, dst, _ = graph._graph.edges()
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    n_cols = {k: th.split(v, bnn, 0) for k, v in graph._node_frame.items()}
+    e_cols = {k: th.split(v, bne, 0) for k, v in graph._edge_frame.items()}
+    out, n0, e0 = [], 0, 0
+    for i, (n, m) in enumerate(zip(bnn, bne)):
+        index = GraphIndex(0)
+        index.add_nodes(n)
+        if m:
+            index.add_edges(src[e0:e0 + m] - n0, dst[e0:e0 + m] - n0)
+        out.append(DGLGraph(index, {k: c[i] for k, c in n_cols.items()},
+                            {k: c[i] for k, c in e_cols.items()}))
+        n0 += n
+        e0 += m
+    return out

@@ -1083,3 +1083,133 @@ def rgcn_layer1_backward(graph, hidden, weight, norm, grad_out, grad_hidden, gra
         ctypes.byref(g), _arr(hidden, "hidden"), _arr(weight, "weight"), _arr(norm, "norm"),
         _arr(grad_out, "grad_out"), _arr(grad_hidden, "grad_hidden"),
         _arr(grad_weight, "grad_weight"), _stream(grad_out)))
+
+
+# ---- segment kernels (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -------------------
+class Segments:
+    """The row segments of a batch for the DGLMISegment* entries: ``offsets`` a device
+    int64 tensor of B + 1 non-decreasing values from 0 to the row count ``num_rows``
+    (``DGLGraph._segments``).  The caller states ``num_rows``: reading it back from
+    ``offsets`` would synchronise with the device."""
+
+    def __init__(self, offsets, num_rows):
+        if not isinstance(offsets, th.Tensor) or offsets.dtype != th.int64 or offsets.dim() != 1 \
+                or offsets.shape[0] < 1 or not offsets.is_contiguous():
+            raise DGLError("segment offsets must be a contiguous 1-D int64 tensor of B + 1 values")
+        if offsets.device.type != "cuda":
+            raise DGLError("segment offsets are on %s: the MI355X engine runs on ROCm devices only"
+                           % offsets.device)
+        self.offsets = offsets
+        self.num_segments = int(offsets.shape[0]) - 1
+        self.num_rows = int(num_rows)
+        self.device = offsets.device
+
+    def cstruct(self, row_floats, workspace="reduce"):
+        """The call's DGLMISegments; ``workspace``: "reduce" (carries), "softmax" (carries
+        and the statistics tables) or None."""
+        s = _ffi.Segments()
+        s.offsets = self.offsets.data_ptr()
+        s.num_segments = self.num_segments
+        s.num_rows = self.num_rows
+        size = {"reduce": _ffi.lib().DGLMISegmentWorkspaceBytes,
+                "softmax": _ffi.lib().DGLMISegmentSoftmaxWorkspaceBytes}.get(workspace)
+        nbytes = size(self.num_rows, self.num_segments, int(row_floats)) if size else 0
+        ws = th.empty(int(nbytes), dtype=th.uint8, device=self.device) if nbytes > 0 else None
+        s.workspace = ws.data_ptr() if ws is not None else None
+        s.workspace_bytes = int(nbytes)
+        s._keep = (ws, self.offsets)
+        return s
+
+
+def segment_chunk_rows(row_floats):
+    """Rows of one chunk of the segment walk at this row width (DGLMISegmentChunkRows)."""
+    return int(_ffi.lib().DGLMISegmentChunkRows(int(row_floats)))
+
+
+def _seg_ctx(seg, tensors):
+    for name, t in tensors:
+        if t is not None and t.device != seg.device:
+            raise DGLError("Expected device context %s. But got %s for %s." % (seg.device, t.device, name))
+
+
+def segment_reduce(reducer, seg, feat, mul, out, arg=None):
+    """out[b] = reduce of feat[i] (* mul[i]) over the rows of segment b -> DGLMISegmentReduce.
+    ``arg`` (B, F) int64 for max / min."""
+    _seg_ctx(seg, [("feat", feat), ("mul", mul), ("out", out), ("arg", arg)])
+    if arg is not None and (arg.dtype != th.int64 or not arg.is_contiguous()
+                            or arg.numel() != out.numel()):
+        raise DGLError("arg must be a contiguous int64 tensor of out's size")
+    s = seg.cstruct(_feat_len(feat))
+    if arg is not None and arg.numel() == 0:
+        # an empty arg still tells max / min apart from sum: a real one-element buffer
+        arg = th.empty(1, dtype=th.int64, device=seg.device)
+    argp = None if arg is None else ctypes.c_void_p(arg.data_ptr())
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentReduce(
+            reducer.encode(), ctypes.byref(s), _arr(feat, "feat"), _arr(mul, "mul"), _arr(out, "out"),
+            argp, _stream(out)))
+    return out
+
+
+def _row_scalars(t, name, n):
+    if t is None:
+        return None
+    if t.dtype != th.float32 or not t.is_contiguous() or t.numel() != n:
+        raise DGLError("%s must be a contiguous float32 tensor of %d values" % (name, n))
+    return ctypes.c_void_p(t.data_ptr() if t.numel() else None)
+
+
+def segment_broadcast(seg, v, out, row_scale=None, divide_by_length=False):
+    """out[i] = v[seg of i] (/ max(len, 1)) (* row_scale[i]) -> DGLMISegmentBroadcast."""
+    _seg_ctx(seg, [("v", v), ("out", out), ("row_scale", row_scale)])
+    s = seg.cstruct(_feat_len(v), workspace=None)
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentBroadcast(
+            ctypes.byref(s), _arr(v, "v"), _row_scalars(row_scale, "row_scale", seg.num_rows),
+            int(bool(divide_by_length)), _arr(out, "out"), _stream(out)))
+    return out
+
+
+def segment_rowdot(seg, x, v, out):
+    """out[i] = <x[i], v[seg of i]> -> DGLMISegmentRowDot (its header fixes the order)."""
+    _seg_ctx(seg, [("x", x), ("v", v), ("out", out)])
+    s = seg.cstruct(_feat_len(x), workspace=None)
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentRowDot(
+            ctypes.byref(s), _arr(x, "x"), _arr(v, "v"), _row_scalars(out, "out", seg.num_rows),
+            _stream(out)))
+    return out
+
+
+def segment_softmax_forward(seg, logits, out):
+    """Softmax of every column over each segment -> DGLMISegmentSoftmaxForward."""
+    _seg_ctx(seg, [("logits", logits), ("out", out)])
+    s = seg.cstruct(_feat_len(logits), workspace="softmax")
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentSoftmaxForward(
+            ctypes.byref(s), _arr(logits, "logits"), _arr(out, "out"), _stream(out)))
+    return out
+
+
+def segment_softmax_backward(seg, out, grad_out, grad_logits):
+    """grad_logits = out * grad_out - out * segment_sum(out * grad_out)."""
+    _seg_ctx(seg, [("out", out), ("grad_out", grad_out), ("grad_logits", grad_logits)])
+    s = seg.cstruct(_feat_len(out), workspace="softmax")
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentSoftmaxBackward(
+            ctypes.byref(s), _arr(out, "out"), _arr(grad_out, "grad_out"),
+            _arr(grad_logits, "grad_logits"), _stream(out)))
+    return grad_logits
+
+
+def segment_scatter_arg(seg, arg, grad_out, grad_feat):
+    """grad_feat[arg[b, f], f] = grad_out[b, f] where arg >= 0; grad_feat zero-filled."""
+    _seg_ctx(seg, [("arg", arg), ("grad_out", grad_out), ("grad_feat", grad_feat)])
+    if arg.dtype != th.int64 or not arg.is_contiguous() or arg.numel() != grad_out.numel():
+        raise DGLError("arg must be a contiguous int64 tensor of grad_out's size")
+    s = seg.cstruct(_feat_len(grad_out), workspace=None)
+    with th.cuda.device(seg.device):
+        check_call(_ffi.lib().DGLMISegmentScatterArg(
+            ctypes.byref(s), ctypes.c_void_p(arg.data_ptr() if arg.numel() else None),
+            _arr(grad_out, "grad_out"), _arr(grad_feat, "grad_feat"), _stream(grad_feat)))
+    return grad_feat

@@ -4,4 +4,6 @@ from .conv import (GraphConv, GATConv, FusedGATConv, RelGraphConv, SAGEConv,  # 
                    GatedGraphConv, DenseGraphConv,
                    DenseSAGEConv, DenseChebConv)
 from .softmax import edge_softmax  # noqa: F401
+from .glob import (SumPooling, AvgPooling, MaxPooling, SortPooling,  # noqa: F401
+                   GlobalAttentionPooling, Set2Set, WeightAndSum)
 from .hetero import HeteroGraphConv  # noqa: F401

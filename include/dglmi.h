@@ -730,6 +730,71 @@ int DGLMIPartitionLabelProp(const DGLMIGraph* graph, int32_t num_parts, int32_t 
                             int32_t* assign, int64_t* part_loads, int64_t* cut_edges,
                             void* stream);
 
+/* ---- batched graphs: segment kernels (extension) ----------------------------
+ * A batch of graphs (dgl.batch) keeps the nodes, and the edges, of graph b in rows
+ * offsets[b] .. offsets[b + 1] of its frames.  The readout functions reduce, broadcast
+ * and normalise over those segments.  The reference does it with scatter_add_ over a
+ * host-built segment id (backend/pytorch/tensor.py:228-239) and by padding every graph
+ * to the largest (readout.py:396-432); these entries walk the rows once, in position
+ * order, in fixed chunks of whole rows whatever the segment sizes, without atomics on
+ * data: the same bits on every run.
+ *   offsets: device int64, num_segments + 1 values, non-decreasing, offsets[0] = 0 and
+ *     offsets[num_segments] = num_rows; segments may be empty;
+ *   workspace: optional scratch, 16-byte aligned: DGLMISegmentWorkspaceBytes bytes (the
+ *     walk's carries and counters) for the reduce, DGLMISegmentSoftmaxWorkspaceBytes (the
+ *     same plus two per-segment statistics tables) for the two softmax entries; the
+ *     other entries need none.  NULL, misaligned or too small is no error: the call
+ *     then takes a stream-ordered allocation, as every entry with a workspace here does.
+ * Arrays are fp32, contiguous and 16-byte aligned; F is the product of the trailing
+ * dimensions and must agree between the arrays of a call.  num_rows == 0 or
+ * num_segments == 0 is no error: outputs still take their identities. */
+typedef struct {
+  const int64_t* offsets;
+  int64_t num_segments;
+  int64_t num_rows;
+  void* workspace;
+  int64_t workspace_bytes;
+} DGLMISegments;
+int64_t DGLMISegmentWorkspaceBytes(int64_t num_rows, int64_t num_segments, int64_t row_floats);
+int64_t DGLMISegmentSoftmaxWorkspaceBytes(int64_t num_rows, int64_t num_segments,
+                                          int64_t row_floats);
+/* Rows of the table one workgroup walks at this row width (the chunk; tests build
+ * segment lengths around it). */
+int64_t DGLMISegmentChunkRows(int64_t row_floats);
+/* out[b, f] = reduce over the rows i of segment b of feat[i, f] * mul, reducer "sum" |
+ * "max" | "min".  mul NULL: none; mul with num_rows elements: one scalar per row (4-byte
+ * aligned is enough); mul shaped like feat: elementwise.  The product is rounded, then reduced.  Empty segments
+ * get 0 / -inf / +inf.  max / min also write arg[b, f] (num_segments x F int64): the
+ * lowest row that attains the value, -1 for an empty segment; a NaN in the segment makes
+ * the value NaN and arg its first NaN row (numpy.max / argmax).  arg must be NULL for sum. */
+int DGLMISegmentReduce(const char* reducer, const DGLMISegments* seg, const DGLMIArray* feat,
+                       const DGLMIArray* mul, DGLMIArray* out, int64_t* arg, void* stream);
+/* out[i, :] = v[seg of i, :], divided by max(segment length, 1) when divide_by_length,
+ * then multiplied by row_scale[i] (num_rows floats) when given. */
+int DGLMISegmentBroadcast(const DGLMISegments* seg, const DGLMIArray* v, const float* row_scale,
+                          int divide_by_length, DGLMIArray* out, void* stream);
+/* out[i] = sum over f of x[i, f] * v[seg of i, f] (num_rows floats).  Each product is
+ * rounded, then added.  Order over f: with VW = 4 / 2 / 1 for F % 4 == 0 / F even / odd
+ * and L = the least power of two >= F / VW (64 at the most), lane t of L adds slots t,
+ * t + L, ... in ascending column order, and the L partials are combined pairwise at lane
+ * distances 1, 2, 4, ... */
+int DGLMISegmentRowDot(const DGLMISegments* seg, const DGLMIArray* x, const DGLMIArray* v,
+                       float* out, void* stream);
+/* Softmax of every column over each segment: out[i, f] = exp(s[i, f] - m[b, f]) / l[b, f]
+ * with m the segment's maximum and l its sum of exp(s - m), merged online.  Backward:
+ * grad_logits = out * grad_out - out * S[b], S = the segment sums of out * grad_out
+ * (softmax.py:103-112). */
+int DGLMISegmentSoftmaxForward(const DGLMISegments* seg, const DGLMIArray* logits,
+                               DGLMIArray* out, void* stream);
+int DGLMISegmentSoftmaxBackward(const DGLMISegments* seg, const DGLMIArray* out,
+                                const DGLMIArray* grad_out, DGLMIArray* grad_logits,
+                                void* stream);
+/* The max / min gradient: grad_feat[arg[b, f], f] = grad_out[b, f] where arg[b, f] >= 0;
+ * grad_feat (num_rows x F) must be zero-filled by the caller (targets are unique: plain
+ * stores).  arg as written by the reduce for the same segments. */
+int DGLMISegmentScatterArg(const DGLMISegments* seg, const int64_t* arg,
+                           const DGLMIArray* grad_out, DGLMIArray* grad_feat, void* stream);
+
 /* ---- measurement utility (bench.py; no reference counterpart) -------------
  * dst[i] = src[i] for num_floats fp32 values (a multiple of 4, both 16-B aligned)
  * by a float4 streaming copy: the access pattern MI355X_MICROARCH.md quotes the
