@@ -44,6 +44,15 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr float kNegInf = -__builtin_huge_valf();
+// The forward's running maximum starts here, not at -inf: a logit of -inf (a masked edge)
+// met before any finite one then fails `s > mx` and takes the weight fexp(-inf - kNoMax) = 0,
+// where -inf - -inf gave NaN and poisoned the row.  Every finite logit is >= kNoMax, and the
+// first one rescales the still-zero sums by fexp(kNoMax - s) = 0 as fexp(-inf) did: finite
+// inputs keep their bits, and the edge loop has no new instruction.  A row (or a chunk piece,
+// or a column block's part) that met only -inf logits ends with m = kNoMax and l = 0; the
+// flush, the fixup and the merge make a row with edges and l = 0 NaN (a softmax over nothing,
+// as the edge-softmax entries do); a row without edges stays 0 (zero_row: m = l = 0).
+constexpr float kNoMax = -__FLT_MAX__;
 
 __device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4g(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -240,7 +249,7 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd(GatArgs a) {
   float4 acc[NV], qa[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    mx[v] = kNegInf;
+    mx[v] = kNoMax;
     sm[v] = 0.0f;
     acc[v] = Z;
     qs[v] = 0.0f;
@@ -266,7 +275,8 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd(GatArgs a) {
         float4 o = acc[v], q = qa[v];
         float qsv = qs[v];
         if (final && !a.raw) {
-          const float inv = sm[v] > 0.0f ? 1.0f / sm[v] : 0.0f;
+          // l = 0: every logit of the row was -inf (a row without edges never gets here)
+          const float inv = sm[v] == 0.0f ? __builtin_nanf("") : 1.0f / sm[v];
           o = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
           q = make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
           qsv *= inv;
@@ -360,7 +370,7 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd(GatArgs a) {
           cont = false;
 #pragma unroll
           for (int v = 0; v < NV; ++v) {
-            mx[v] = kNegInf;
+            mx[v] = kNoMax;
             sm[v] = 0.0f;
             acc[v] = Z;
             qs[v] = 0.0f;
@@ -460,7 +470,8 @@ __global__ void __launch_bounds__(kBlock) k_gat_fwd_fixup(GatArgs a) {
       float qs = LS ? ps[h] : 0.0f;
       for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) merge(acc, mx, sm, qa, qs, c, f4, h);
       if (head) {
-        const float inv = a.raw ? 1.0f : (sm > 0.0f ? 1.0f / sm : 0.0f);
+        // a split row has edges: l = 0 means that every one of its logits was -inf
+        const float inv = a.raw ? 1.0f : (sm == 0.0f ? __builtin_nanf("") : 1.0f / sm);
         acc = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
         if (LS) {
           qa = make_float4(qa.x * inv, qa.y * inv, qa.z * inv, qa.w * inv);
@@ -870,11 +881,15 @@ __global__ void __launch_bounds__(kBlock) k_gat_merge(const float* __restrict__ 
     const int h = (4 * f4) / D;
     float mx = kNegInf, sm = 0.0f, qs = 0.0f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), qa = acc;
+    bool masked = false;  // some block held edges of the row, every one with a -inf logit
     for (int b = 0; b < nb; ++b) {
       const int64_t hi = (static_cast<int64_t>(b) * num_rows + r) * H + h;
       const float lb = l_part[hi];
-      if (!(lb > 0.0f)) continue;
       const float mb = m_part[hi];
+      if (lb == 0.0f) {  // no edge of the row in this block (m = 0), or masked ones only
+        masked = masked || mb == kNoMax;
+        continue;
+      }  // a NaN part (a +inf or NaN logit in the block) is merged, not skipped
       const int64_t vi = (static_cast<int64_t>(b) * num_rows + r) * F + 4 * f4;
       const float4 ab = ld4g(out_part + vi);
       const float mn = fmaxf(mx, mb);
@@ -890,12 +905,14 @@ __global__ void __launch_bounds__(kBlock) k_gat_merge(const float* __restrict__ 
       }
       mx = mn;
     }
-    const float inv = sm > 0.0f ? 1.0f / sm : 0.0f;
+    const float inv = sm != 0.0f ? 1.0f / sm : (masked ? __builtin_nanf("") : 0.0f);
     st4g(out + r * F + 4 * f4, make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv));
     if (lf_part != nullptr)
       st4g(lf + r * F + 4 * f4, make_float4(qa.x * inv, qa.y * inv, qa.z * inv, qa.w * inv));
     if ((4 * f4) % D == 0) {
-      m[r * H + h] = sm > 0.0f ? mx : 0.0f;
+      // (m, l) as the unblocked walk leaves them: (kNoMax, 0) for a row masked everywhere,
+      // (0, 0) for a row without edges
+      m[r * H + h] = sm != 0.0f ? mx : (masked ? kNoMax : 0.0f);
       l[r * H + h] = sm;
       if (lf_part != nullptr) ls[r * H + h] = qs * inv;
     }

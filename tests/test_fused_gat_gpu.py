@@ -1,7 +1,8 @@
 """Fused GAT kernel vs the unfused builtin composition (the hack's own
 examples/pytorch/gat/fused_gat_unit_test.py strategy: 65,536 nodes, every node
 -> hub 0 and hub 1, 8 heads x 8 hidden, slope 0.2) and vs a dense fp64
-restatement on a skewed graph with empty rows."""
+restatement on a skewed graph with empty rows.
+Every lane configuration, chunk length and special logit: tests/test_gat_shapes_gpu.py."""
 import numpy as np
 import pytest
 import torch as th

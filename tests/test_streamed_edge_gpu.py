@@ -183,9 +183,11 @@ def test_mapped_u_mul_e_on_identity_edge_ids(route, monkeypatch):
     ref = th.zeros(n, D, device=DEV)
     K.binary_op_reduce("sum", "mul", g0._graph.get_immutable_gidx(DEV), "src", "edge", x, w, ref,
                        lhs_map=lhs_map)
-    exact = (x[lhs_map.long()][th.as_tensor(src).long().to(DEV)] * w)
-    exact = th.zeros(n, D, device=DEV).index_add_(0, th.as_tensor(dst).long().to(DEV), exact)
-    assert th.allclose(ref, exact, rtol=1e-4, atol=1e-4)
+    # fp64: an fp32 index_add_ sums a hub row's thousands of terms by atomics, in an order that
+    # changes from run to run, so its own error did too (the kernel's sum is deterministic)
+    exact = (x.double()[lhs_map.long()][th.as_tensor(src).long().to(DEV)] * w.double())
+    exact = th.zeros(n, D, dtype=th.float64, device=DEV).index_add_(0, th.as_tensor(dst).long().to(DEV), exact)
+    assert th.allclose(ref.double(), exact, rtol=1e-4, atol=1e-4)
     if route == "dst_sorted":
         monkeypatch.setenv("DGLMI_EID_IDENTITY", "1")
         g1 = dgl.DGLGraph()
