@@ -2877,4 +2877,51 @@ int DGLMISegmentScatterArg(const DGLMISegments* seg, const int64_t* arg,
   API_END();
 }
 
+// ---- k nearest neighbours inside segments (kernels_knn.hip) -------------------
+int32_t DGLMIKnnMaxK(void) { return knn_max_k(); }
+
+int DGLMIKnnTile(int64_t D, int32_t k, int32_t* query_rows, int32_t* cand_rows,
+                 int32_t* feat_chunk) {
+  API_BEGIN();
+  DGLMI_CHECK(query_rows && cand_rows && feat_chunk, "null argument");
+  DGLMI_CHECK(D >= 1, "knn: points need at least one coordinate");
+  DGLMI_CHECK(k >= 1 && k <= knn_max_k(),
+              "knn: k must be between 1 and " + std::to_string(knn_max_k()) + ", got " +
+                  std::to_string(k));
+  int tq = 0, tc = 0, dc = 0;
+  knn_tile(D, k, &tq, &tc, &dc);
+  *query_rows = tq;
+  *cand_rows = tc;
+  *feat_chunk = dc;
+  API_END();
+}
+
+int DGLMIKnnSelect(const DGLMISegments* seg, const DGLMIArray* x, int32_t k, int32_t* nbr,
+                   float* dist, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(k >= 1 && k <= knn_max_k(),
+              "knn: k must be between 1 and " + std::to_string(knn_max_k()) + ", got " +
+                  std::to_string(k));
+  DGLMI_CHECK(seg != nullptr && seg->offsets != nullptr, "null segments");
+  DGLMI_CHECK(seg->num_segments >= 0 && seg->num_rows >= 0, "negative segment or row count");
+  check_array(x, "x");
+  DGLMI_CHECK(x->ndim == 2, "knn: x must be (N, D)");
+  const int64_t N = x->shape[0], D = x->shape[1];
+  DGLMI_CHECK(N == seg->num_rows, "knn: x has " + std::to_string(N) + " rows, the segments " +
+                                      std::to_string(seg->num_rows));
+  DGLMI_CHECK(D >= 1, "knn: points need at least one coordinate");
+  DGLMI_CHECK(N * static_cast<int64_t>(k) < (int64_t(1) << 31) && N < (int64_t(1) << 31),
+              "knn: N * k must stay below 2^31");
+  if (N == 0) return 0;
+  DGLMI_CHECK(seg->num_segments > 0, "rows without segments");
+  DGLMI_CHECK(nbr != nullptr, "null nbr");
+  hipPointerAttribute_t at;
+  check_hip(hipPointerGetAttributes(&at, seg->offsets), "segment offsets: not a device pointer");
+  DeviceGuard guard(at.device);
+  launch_knn_select(x->data, seg->offsets, seg->num_segments, N, D, k, nbr, dist,
+                    static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "knn select launch");
+  API_END();
+}
+
 }  // extern "C"

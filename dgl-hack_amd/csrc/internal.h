@@ -771,4 +771,11 @@ void launch_seg_rowdot(const SegRowArgs& a, hipStream_t s);
 void launch_seg_scatter_arg(const int64_t* arg, const float* gy, int64_t B, int64_t F,
                             int64_t num_rows, float* out, hipStream_t s);
 
+// k nearest neighbours inside segments (kernels_knn.hip): nbr / dist (N, k), see
+// DGLMIKnnSelect.  knn_tile: the instance's query rows, candidate rows and feature chunk.
+int knn_max_k();
+void knn_tile(int64_t D, int k, int* tq, int* tc, int* dc);
+void launch_knn_select(const float* x, const int64_t* offsets, int64_t num_segments, int64_t N,
+                       int64_t D, int k, int32_t* nbr, float* dist, hipStream_t s);
+
 }  // namespace dglmi

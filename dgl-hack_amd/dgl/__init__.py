@@ -21,7 +21,7 @@ from .heterograph import (DGLHeteroGraph, heterograph, graph, bipartite,  # noqa
                           hetero_from_relations)
 from .transform import (laplacian_lambda_max, add_self_loop, remove_self_loop,  # noqa: F401
                         reverse, to_bidirected, metis_partition,
-                        partition_graph_with_halo)
+                        partition_graph_with_halo, knn_graph, segmented_knn_graph)
 from . import transform  # noqa: F401
 from . import data  # noqa: F401
 from . import nn  # noqa: F401

@@ -398,6 +398,13 @@ _SIGS = {
     "DGLMISegmentScatterArg": (ctypes.c_int, [
         ctypes.POINTER(Segments), ctypes.c_void_p, ctypes.POINTER(Array), ctypes.POINTER(Array),
         ctypes.c_void_p]),
+    "DGLMIKnnMaxK": (ctypes.c_int32, []),
+    "DGLMIKnnTile": (ctypes.c_int, [
+        ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "DGLMIKnnSelect": (ctypes.c_int, [
+        ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -1213,3 +1213,43 @@ def segment_scatter_arg(seg, arg, grad_out, grad_feat):
             ctypes.byref(s), ctypes.c_void_p(arg.data_ptr() if arg.numel() else None),
             _arr(grad_out, "grad_out"), _arr(grad_feat, "grad_feat"), _stream(grad_feat)))
     return grad_feat
+
+
+# ---- k nearest neighbours inside segments (dgl.knn_graph / segmented_knn_graph) ----------
+def knn_max_k():
+    """The largest k of ``knn_select`` (DGLMIKnnMaxK)."""
+    return int(_ffi.lib().DGLMIKnnMaxK())
+
+
+def knn_tile(D, k):
+    """(query rows, candidate rows, feature chunk) of the kernel instance that serves
+    points of ``D`` coordinates at ``k`` (DGLMIKnnTile)."""
+    tq, tc, dc = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    check_call(_ffi.lib().DGLMIKnnTile(int(D), int(k), ctypes.byref(tq), ctypes.byref(tc),
+                                       ctypes.byref(dc)))
+    return tq.value, tc.value, dc.value
+
+
+def knn_select(x, offsets, k, want_dist=False):
+    """The k nearest rows of every row of ``x`` (N, D) inside its own segment ->
+    DGLMIKnnSelect (its header states the distance, the order and the limits).  ``offsets``:
+    device int64, B + 1 values.  Returns ``nbr`` (N, k) int32 global row ids, and ``dist``
+    (N, k) float32 with ``want_dist``; a segment shorter than k leaves -1 / +inf tails."""
+    if not isinstance(x, th.Tensor) or x.dim() != 2:
+        raise DGLError("x must be an (N, D) tensor")
+    if x.device.type != "cuda":
+        raise DGLError("x is on %s: the MI355X engine runs on ROCm devices only" % x.device)
+    seg = Segments(offsets, x.shape[0])
+    _seg_ctx(seg, [("x", x)])
+    k = int(k)
+    n = int(x.shape[0])
+    if n * max(k, 0) >= 2 ** 31:  # before the outputs are allocated
+        raise DGLError("knn: N * k must stay below 2^31, got %d * %d" % (n, k))
+    nbr = th.empty((n, max(k, 0)), dtype=th.int32, device=x.device)
+    dist = th.empty((n, max(k, 0)), dtype=th.float32, device=x.device) if want_dist else None
+    s = seg.cstruct(x.shape[1], workspace=None)
+    with th.cuda.device(x.device):
+        check_call(_ffi.lib().DGLMIKnnSelect(
+            ctypes.byref(s), _arr(x, "x"), k, ctypes.c_void_p(nbr.data_ptr() if nbr.numel() else None),
+            ctypes.c_void_p(dist.data_ptr() if want_dist and dist.numel() else None), _stream(x)))
+    return (nbr, dist) if want_dist else nbr

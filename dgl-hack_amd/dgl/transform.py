@@ -207,3 +207,85 @@ def metis_partition(g, k, extra_cached_hops=0, method=None):
     for pid, sub in parts.items():
         sub.ndata["part_id"] = th.from_numpy(part[sub.parent_nid.numpy()])
     return parts
+
+
+def _knn_graph(x, k, segs, what):
+    """The k-NN graph of the point sets ``segs`` (host ints) of ``x`` (N, D).  Everything
+    is checked on the host before the first launch; no index visits the host after it."""
+    import torch as th
+    from . import kernel as K
+    from ._ffi import DGLError
+    from .graph import DGLGraph
+    if not isinstance(x, th.Tensor) or x.dtype != th.float32:
+        raise DGLError("%s: x must be a float32 tensor, got %s"
+                       % (what, x.dtype if isinstance(x, th.Tensor) else type(x)))
+    n = int(x.shape[0])
+    k = int(k)
+    if k < 1:
+        raise DGLError("%s: k must be at least 1, got %d" % (what, k))
+    if k > K.knn_max_k():
+        raise DGLError("%s: k = %d is above the kernel's limit of %d neighbours"
+                       % (what, k, K.knn_max_k()))
+    if any(s < 0 for s in segs) or sum(segs) != n:
+        raise DGLError("%s: the point sets hold %d points, x has %d rows" % (what, sum(segs), n))
+    short = [s for s in segs if s < k]
+    if short:
+        raise DGLError("%s: a point set of %d points has fewer than k = %d" % (what, short[0], k))
+    if n * k >= 2 ** 31:
+        raise DGLError("%s: %d points times k = %d reaches 2^31 edges" % (what, n, k))
+    if x.device.type != "cuda":
+        raise DGLError("x is on %s: the MI355X engine runs on ROCm devices only" % x.device)
+    x = x.detach().contiguous()  # the graph is not differentiable
+    off = np.zeros(len(segs) + 1, np.int64)
+    np.cumsum(np.asarray(segs, np.int64), out=off[1:])
+    offsets = th.from_numpy(off).to(x.device)
+    nbr = K.knn_select(x, offsets, k)
+    # edges run neighbour -> point.  The reference's csr_matrix((1, (nbr, point))).tocoo()
+    # numbers them in ascending (neighbour, point) order: the (N, k) table is point-major,
+    # so one stable sort by neighbour gives exactly that.
+    src, perm = th.sort(nbr.reshape(-1), stable=True)
+    dst = th.div(perm, k, rounding_mode="floor").to(th.int32)
+    g = DGLGraph.from_device_coo(src.contiguous(), dst.contiguous(), n)
+    # extension: the result is a batch of its point sets (a set's sources are one
+    # contiguous id range, so its k * s edges are contiguous in the edge order above)
+    if len(segs) > 1:
+        g._batch_num_nodes = [int(s) for s in segs]
+        g._batch_num_edges = [k * int(s) for s in segs]
+        g._segment_cache[("nodes", str(x.device))] = ((len(segs), n), offsets)
+    return g
+
+
+def knn_graph(x, k):
+    """The graph whose nodes are the points ``x`` and in which the predecessors of a point
+    are its ``k`` nearest points, itself included (``transform.py:55-98``).  ``x``: (M, D),
+    or (B, M, D) for B point sets of M points each, whose graphs are unioned: point j of
+    set i is node i * M + j.  Edge ids are the reference's: ascending (source, destination).
+
+    Built on the device by one fused distance / selection kernel (``dgl.kernel.knn_select``);
+    the distance is sum_f (a_f - b_f)^2, not the reference's |a|^2 + |b|^2 - 2 a.b, and ties
+    go to the lower node id.  The graph is read-only, has ``x.shape[0]`` (x B) nodes whatever
+    the largest neighbour id, and -- an extension -- is a batch of its B point sets
+    (``batch_num_nodes`` = M each, ``batch_num_edges`` = k M each), so ``dgl.max_nodes``,
+    ``MaxPooling`` and ``dgl.unbatch`` work on it directly."""
+    import torch as th
+    from ._ffi import DGLError
+    if not isinstance(x, th.Tensor) or x.dim() not in (2, 3):
+        raise DGLError("knn_graph: x must be an (M, D) or (B, M, D) tensor")
+    if x.dim() == 2:
+        segs = [int(x.shape[0])]
+    else:
+        segs = [int(x.shape[1])] * int(x.shape[0])
+        x = x.reshape(-1, x.shape[2])
+    return _knn_graph(x, k, segs, "knn_graph")
+
+
+def segmented_knn_graph(x, k, segs):
+    """:func:`knn_graph` for point sets of different sizes (``transform.py:101-141``):
+    ``x`` (N, D) holds the sets one after another, ``segs`` (a host iterable of ints summing
+    to N) their sizes.  The result is the batch of the sets' graphs (``batch_num_nodes`` =
+    ``segs``); the per-set Python loop of the reference is one kernel launch here."""
+    import torch as th
+    from ._ffi import DGLError
+    if not isinstance(x, th.Tensor) or x.dim() != 2:
+        raise DGLError("segmented_knn_graph: x must be an (N, D) tensor")
+    return _knn_graph(x, k, [int(s) for s in segs], "segmented_knn_graph")

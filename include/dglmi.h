@@ -795,6 +795,39 @@ int DGLMISegmentSoftmaxBackward(const DGLMISegments* seg, const DGLMIArray* out,
 int DGLMISegmentScatterArg(const DGLMISegments* seg, const int64_t* arg,
                            const DGLMIArray* grad_out, DGLMIArray* grad_feat, void* stream);
 
+/* ---- k nearest neighbours inside segments (extension) -----------------------
+ * The graph construction of dgl.knn_graph / segmented_knn_graph (transform.py:45-141) as
+ * one kernel: squared distances and the selection of the k smallest, fused, so no (N, M)
+ * distance matrix is written and no index visits the host.
+ *   x: (N, D) fp32, contiguous, D >= 1 (rows need no alignment: D = 3 is the common case);
+ *   seg: the point sets, rows offsets[b] .. offsets[b + 1] of x (the contract of
+ *     DGLMISegments above: num_segments + 1 device int64 values, non-decreasing, 0 .. N;
+ *     empty segments allowed; num_rows = N).  The workspace fields are not used: the
+ *     kernel needs none.
+ *   nbr: (N, k) device int32, global row ids; dist: (N, k) device fp32, or NULL (not written).
+ * Distance.  d(i, j) = sum over f, in ascending f, of (x[i, f] - x[j, f])^2 in fp32: a
+ *   rounded subtraction, a rounded square, a rounded add.  It is not the reference's
+ *   |a|^2 + |b|^2 - 2 a.b, which cancels for near neighbours: here d(i, i) is exactly 0
+ *   and, every term being non-negative, the relative error is at most gamma_(D+2).
+ * Candidates of row i: the rows of i's own segment, i included (the reference keeps the
+ *   self loop too).
+ * Order.  Row i of nbr holds the k smallest candidates under the strict total order
+ *   (d ascending, a NaN distance after every number, then row id ascending): ties go to
+ *   the lower id, and the result is a function of x alone -- the same bits on every run.
+ *   A NaN distance is written to dist as the canonical quiet NaN.
+ * Short segments.  A segment of fewer than k rows has fewer than k candidates: the
+ *   missing trailing entries are -1 in nbr and +inf in dist (no error: the entry could
+ *   not know without a host synchronisation).
+ * Limits.  1 <= k <= DGLMIKnnMaxK() (64) and N * k < 2^31; otherwise -1 with a message.
+ * DGLMIKnnTile: the shipped instance's query-tile rows (one workgroup's consecutive rows),
+ *   candidate-tile rows and feature-chunk length for (D, k); tests build their shapes
+ *   around these.  Returns -1 for D < 1 or k outside the limits. */
+int32_t DGLMIKnnMaxK(void);
+int DGLMIKnnTile(int64_t D, int32_t k, int32_t* query_rows, int32_t* cand_rows,
+                 int32_t* feat_chunk);
+int DGLMIKnnSelect(const DGLMISegments* seg, const DGLMIArray* x, int32_t k, int32_t* nbr,
+                   float* dist, void* stream);
+
 /* ---- measurement utility (bench.py; no reference counterpart) -------------
  * dst[i] = src[i] for num_floats fp32 values (a multiple of 4, both 16-B aligned)
  * by a float4 streaming copy: the access pattern MI355X_MICROARCH.md quotes the
