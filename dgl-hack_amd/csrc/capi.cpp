@@ -2924,4 +2924,111 @@ int DGLMIKnnSelect(const DGLMISegments* seg, const DGLMIArray* x, int32_t k, int
   API_END();
 }
 
+// ---- neighbour sampling, row gathers, block relabelling (kernels_sample.hip) ----
+namespace {
+
+SampleCsr sample_csr(const DGLMICsr* csr, int32_t num_bits) {
+  DGLMI_CHECK(csr != nullptr && csr->indptr != nullptr, "null csr");
+  DGLMI_CHECK(num_bits == 32 || num_bits == 64, "num_bits must be 32 or 64");
+  DGLMI_CHECK(csr->num_rows >= 0 && csr->nnz >= 0, "negative csr size");
+  DGLMI_CHECK(csr->nnz == 0 || (csr->indices != nullptr && csr->data != nullptr),
+              "csr with entries needs indices and data");
+  const int w = num_bits == 64 ? 1 : 0;
+  return SampleCsr{IdxPtr{csr->indptr, w}, csr->indices, IdxPtr{csr->data, w}, csr->num_rows};
+}
+
+int device_of(const void* p, const char* what) {
+  hipPointerAttribute_t at;
+  check_hip(hipPointerGetAttributes(&at, p), what);
+  return at.device;
+}
+
+}  // namespace
+
+int32_t DGLMISampleMaxFanout(void) { return sample_max_fanout(); }
+
+int DGLMISampleNeighbors(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds,
+                         int64_t num_seeds, int32_t fanout, int32_t replace, uint64_t rng_seed,
+                         uint64_t rng_ctr, int64_t* offsets, int64_t num_out, int32_t* out_nbr,
+                         int64_t* out_eid, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(fanout >= 0 && fanout <= sample_max_fanout(),
+              "sample: fanout must be between 0 and " + std::to_string(sample_max_fanout()) +
+                  ", got " + std::to_string(fanout));
+  const SampleCsr c = sample_csr(csr, num_bits);
+  DGLMI_CHECK(num_seeds >= 0 && num_seeds < (int64_t(1) << 31), "sample: bad seed count");
+  DGLMI_CHECK(num_seeds == 0 || seeds != nullptr, "null seeds");
+  DGLMI_CHECK(offsets != nullptr, "null offsets");
+  DGLMI_CHECK(num_out >= 0, "negative num_out");
+  DeviceGuard guard(device_of(offsets, "sample offsets: not a device pointer"));
+  if (out_nbr == nullptr) {
+    launch_sample_count(c, seeds, num_seeds, fanout, replace != 0, offsets,
+                        static_cast<hipStream_t>(stream));
+  } else {
+    DGLMI_CHECK(out_eid != nullptr, "null out_eid");
+    launch_sample_pick(c, seeds, num_seeds, fanout, replace != 0, rng_seed, rng_ctr, offsets, num_out,
+                       out_nbr, out_eid, static_cast<hipStream_t>(stream));
+  }
+  check_hip(hipGetLastError(), "sample launch");
+  API_END();
+}
+
+int DGLMICsrGatherRows(const DGLMICsr* csr, int32_t num_bits, const int32_t* rows, int64_t num_rows,
+                    int64_t* offsets, int64_t num_out, int32_t* out_nbr, int64_t* out_eid,
+                    void* stream) {
+  API_BEGIN();
+  const SampleCsr c = sample_csr(csr, num_bits);
+  DGLMI_CHECK(num_rows >= 0 && num_rows < (int64_t(1) << 31), "gather rows: bad row count");
+  DGLMI_CHECK(num_rows == 0 || rows != nullptr, "null rows");
+  DGLMI_CHECK(offsets != nullptr, "null offsets");
+  DGLMI_CHECK(num_out >= 0, "negative num_out");
+  DeviceGuard guard(device_of(offsets, "gather offsets: not a device pointer"));
+  if (out_nbr == nullptr) {
+    launch_sample_count(c, rows, num_rows, -1, 0, offsets, static_cast<hipStream_t>(stream));
+  } else {
+    DGLMI_CHECK(out_eid != nullptr, "null out_eid");
+    launch_gather_rows(c, rows, num_rows, offsets, num_out, out_nbr, out_eid,
+                       static_cast<hipStream_t>(stream));
+  }
+  check_hip(hipGetLastError(), "gather rows launch");
+  API_END();
+}
+
+int DGLMIBlockRelabelMark(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                          const int32_t* src, int64_t E, int32_t include_dst, int32_t* flags,
+                          void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(S >= 0 && E >= 0 && S + E < (int64_t(1) << 31), "relabel: S + E must stay below 2^31");
+  DGLMI_CHECK(num_nodes >= 0, "negative num_nodes");
+  if (S + E == 0) return 0;
+  DGLMI_CHECK(table != nullptr && flags != nullptr, "null table or flags");
+  DGLMI_CHECK((S == 0 || dst_nodes != nullptr) && (E == 0 || src != nullptr), "null ids");
+  DeviceGuard guard(device_of(flags, "relabel flags: not a device pointer"));
+  launch_relabel_mark(table, num_nodes, dst_nodes, S, src, E, include_dst != 0, flags,
+                      static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "relabel mark launch");
+  API_END();
+}
+
+int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                           const int32_t* src, int64_t E, int32_t include_dst, const int32_t* flags,
+                           const int32_t* scan, int64_t* src_nodes, int32_t* new_src,
+                           int64_t* counts, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(S >= 0 && E >= 0 && S + E < (int64_t(1) << 31), "relabel: S + E must stay below 2^31");
+  DGLMI_CHECK(num_nodes >= 0, "negative num_nodes");
+  DGLMI_CHECK(counts != nullptr, "null counts");
+  if (S + E > 0) {
+    DGLMI_CHECK(table != nullptr && flags != nullptr && scan != nullptr && src_nodes != nullptr,
+                "null table, flags, scan or src_nodes");
+    DGLMI_CHECK((S == 0 || dst_nodes != nullptr) && (E == 0 || (src != nullptr && new_src != nullptr)),
+                "null ids");
+  }
+  DeviceGuard guard(device_of(counts, "relabel counts: not a device pointer"));
+  launch_relabel_write(table, num_nodes, dst_nodes, S, src, E, include_dst != 0, flags, scan,
+                       src_nodes, new_src, counts, static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "relabel write launch");
+  API_END();
+}
+
 }  // extern "C"

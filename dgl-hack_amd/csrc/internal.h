@@ -778,4 +778,30 @@ void knn_tile(int64_t D, int k, int* tq, int* tc, int* dc);
 void launch_knn_select(const float* x, const int64_t* offsets, int64_t num_segments, int64_t N,
                        int64_t D, int k, int32_t* nbr, float* dist, hipStream_t s);
 
+// neighbour sampling, row gathers and block relabelling (kernels_sample.hip): see
+// DGLMISampleNeighbors, DGLMICsrGatherRows and DGLMIBlockRelabel*.  fanout < 0 in the count:
+// the whole row (the gather's count).
+struct SampleCsr {
+  IdxPtr indptr;
+  const int32_t* indices;
+  IdxPtr data;
+  int64_t num_rows;
+};
+int sample_max_fanout();
+int sample_group_width(int fanout);
+void launch_sample_count(const SampleCsr& c, const int32_t* seeds, int64_t num_seeds, int fanout,
+                         int replace, int64_t* cnt, hipStream_t s);
+void launch_sample_pick(const SampleCsr& c, const int32_t* seeds, int64_t num_seeds, int fanout,
+                        int replace, uint64_t rng_seed, uint64_t rng_ctr, const int64_t* offsets,
+                        int64_t num_out, int32_t* out_nbr, int64_t* out_eid, hipStream_t s);
+void launch_gather_rows(const SampleCsr& c, const int32_t* rows, int64_t n, const int64_t* offsets,
+                        int64_t num_out, int32_t* out_nbr, int64_t* out_eid, hipStream_t s);
+void launch_relabel_mark(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                         const int32_t* src, int64_t E, int include_dst, int32_t* flags,
+                         hipStream_t s);
+void launch_relabel_write(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                          const int32_t* src, int64_t E, int include_dst, const int32_t* flags,
+                          const int32_t* scan, int64_t* src_nodes, int32_t* new_src, int64_t* counts,
+                          hipStream_t s);
+
 }  // namespace dglmi

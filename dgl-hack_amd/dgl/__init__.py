@@ -8,6 +8,7 @@ Drop-in for the reference's message-passing hot path (ydwu4/dgl-hack):
 hand-written HIP kernels for gfx950 (``libdglmi.so``); there is no CPU path.
 """
 from ._ffi import DGLError  # noqa: F401
+from .base import NID, EID  # noqa: F401
 from . import function  # noqa: F401
 from . import backend  # noqa: F401
 from . import kernel  # noqa: F401
@@ -21,8 +22,10 @@ from .heterograph import (DGLHeteroGraph, heterograph, graph, bipartite,  # noqa
                           hetero_from_relations)
 from .transform import (laplacian_lambda_max, add_self_loop, remove_self_loop,  # noqa: F401
                         reverse, to_bidirected, metis_partition,
-                        partition_graph_with_halo, knn_graph, segmented_knn_graph)
+                        partition_graph_with_halo, knn_graph, segmented_knn_graph,
+                        to_block, in_subgraph, out_subgraph)
 from . import transform  # noqa: F401
+from . import sampling  # noqa: F401
 from . import data  # noqa: F401
 from . import nn  # noqa: F401
 

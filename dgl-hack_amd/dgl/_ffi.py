@@ -405,6 +405,21 @@ _SIGS = {
     "DGLMIKnnSelect": (ctypes.c_int, [
         ctypes.POINTER(Segments), ctypes.POINTER(Array), ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMISampleMaxFanout": (ctypes.c_int32, []),
+    "DGLMISampleNeighbors": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMICsrGatherRows": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMIBlockRelabelMark": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMIBlockRelabelWrite": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

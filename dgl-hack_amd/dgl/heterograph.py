@@ -90,6 +90,59 @@ class _Rel:
             self._cache[key] = device_block_gidx(self.n_src, self.n_dst, s, d)
         return self._cache[key]
 
+    def device_uv(self, device):
+        """(src, dst) by edge id as int64 tensors on ``device``."""
+        return th.from_numpy(self.src).to(device), th.from_numpy(self.dst).to(device)
+
+
+class _DeviceRel(_Rel):
+    """A relation built on the device (sampled frontiers, blocks): int32 (src, dst)
+    tensors in edge-id order.  The block index is built from them by ``device_block_gidx``
+    when a kernel first asks; host arrays exist only once a host-side query reads
+    ``src`` / ``dst``."""
+
+    def __init__(self, src, dst, n_src, n_dst):
+        self._dev_src, self._dev_dst = src, dst
+        self.n_src, self.n_dst = int(n_src), int(n_dst)
+        self._cache = {}
+        self._host = None
+
+    def _host_uv(self):
+        if self._host is None:
+            self._host = (self._dev_src.cpu().numpy().astype(np.int64),
+                          self._dev_dst.cpu().numpy().astype(np.int64))
+        return self._host
+
+    @property
+    def src(self):
+        return self._host_uv()[0]
+
+    @property
+    def dst(self):
+        return self._host_uv()[1]
+
+    def number_of_edges(self):
+        return int(self._dev_src.shape[0])
+
+    def edges(self):
+        s, d = self._host_uv()
+        return s, d, np.arange(s.shape[0], dtype=np.int64)
+
+    def device_uv(self, device):
+        return self._dev_src.to(device).long(), self._dev_dst.to(device).long()
+
+    def get_immutable_gidx(self, device):
+        device = th.device(device)
+        if device.type != "cuda":
+            raise DGLError("the MI355X engine runs on ROCm devices only; got device %s" % device)
+        if device.index is None:
+            device = th.device("cuda", th.cuda.current_device())
+        key = str(device)
+        if key not in self._cache:
+            self._cache[key] = device_block_gidx(self.n_src, self.n_dst, self._dev_src.to(device),
+                                                 self._dev_dst.to(device))
+        return self._cache[key]
+
 
 class _NodeSpace:
     def __init__(self, g):
@@ -247,8 +300,7 @@ def _rel_reduce(rel, mfuncs, rfuncs, srcf, dstf, edgef, sel=None, msgs=None):
     dev = _device_of(srcf, dstf, edgef)
     if sel is None:
         gidx = rel.get_immutable_gidx(dev)
-        s = th.from_numpy(rel.src).to(dev)
-        d = th.from_numpy(rel.dst).to(dev)
+        s, d = rel.device_uv(dev)
         ef = edgef
     else:
         s = th.from_numpy(rel.src[sel]).to(dev)
@@ -301,6 +353,23 @@ class DGLHeteroGraph:
         self._nframes = {t: {} for t in self._ntypes}
         self._eframes = {c: {} for c in self._cetypes}
         self._fused = {}
+
+    @classmethod
+    def from_device_coo(cls, cetype, src, dst, n_src, n_dst):
+        """A single-relation graph from device int32 (src, dst) tensors in edge-id order
+        (no host copy, no CSR until a kernel asks): sampled frontiers and blocks."""
+        s, _, d = cetype
+        if s == d and int(n_src) != int(n_dst):
+            raise DGLError("node type %s has different sizes on the two sides" % s)
+        g = cls.__new__(cls)
+        g._ntypes = [s] if s == d else [s, d]
+        g._num_nodes = {s: int(n_src), d: int(n_dst)}
+        g._cetypes = [cetype]
+        g._rels = OrderedDict([(cetype, _DeviceRel(src, dst, n_src, n_dst))])
+        g._nframes = {t: {} for t in g._ntypes}
+        g._eframes = {cetype: {}}
+        g._fused = {}
+        return g
 
     # ---- metadata ---------------------------------------------------------------
     @property
@@ -707,7 +776,7 @@ class _RelationGraph:
         sel = _select(rel, edges)
         m = rel.number_of_edges()
         if sel is None:
-            s, d = th.from_numpy(rel.src).to(dev), th.from_numpy(rel.dst).to(dev)
+            s, d = rel.device_uv(dev)
             gidx, ef, k = rel.get_immutable_gidx(dev), self.edata, m
         else:
             s, d = th.from_numpy(rel.src[sel]).to(dev), th.from_numpy(rel.dst[sel]).to(dev)

@@ -1253,3 +1253,114 @@ def knn_select(x, offsets, k, want_dist=False):
             ctypes.byref(s), _arr(x, "x"), k, ctypes.c_void_p(nbr.data_ptr() if nbr.numel() else None),
             ctypes.c_void_p(dist.data_ptr() if want_dist and dist.numel() else None), _stream(x)))
     return (nbr, dist) if want_dist else nbr
+
+
+# ---- neighbour sampling, row gathers, block relabelling (dgl.sampling, dgl.to_block) -----
+_RELABEL_FREE = 2 ** 31 - 1
+_relabel_tables = {}  # device -> int32 table, all _RELABEL_FREE between calls
+
+
+def sample_max_fanout():
+    """The largest fan-out of ``sample_neighbors`` (DGLMISampleMaxFanout)."""
+    return int(_ffi.lib().DGLMISampleMaxFanout())
+
+
+def _ids32(t, name, device):
+    if not isinstance(t, th.Tensor) or t.dtype != th.int32 or t.device != device or t.dim() != 1:
+        raise DGLError("%s must be a 1-D int32 tensor on %s" % (name, device))
+    return t.contiguous()
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
+def _two_phase(entry, csr, ids, head, tail):
+    """Count phase, running sum, one readback, pick phase: (offsets, nbr, eid)."""
+    dev = csr.indptr.device
+    ids = _ids32(ids, "ids", dev)
+    n = int(ids.shape[0])
+    c = csr.cstruct()
+    offsets = th.empty(n + 1, dtype=th.int64, device=dev)
+    with th.cuda.device(dev):
+        check_call(entry(ctypes.byref(c), csr.bits, _vp(ids), n, *head, _vp(offsets), 0, None, None,
+                         _stream(offsets)))
+        offsets = th.cumsum(offsets, 0)
+        total = int(offsets[-1])  # the call's one readback
+        nbr = th.empty(total, dtype=th.int32, device=dev)
+        eid = th.empty(total, dtype=th.int64, device=dev)
+        if total:
+            check_call(entry(ctypes.byref(c), csr.bits, _vp(ids), n, *head, _vp(offsets), total,
+                             _vp(nbr), _vp(eid), _stream(offsets)))
+    return offsets, nbr, eid
+
+
+def sample_neighbors(csr, seeds, fanout, replace, rng_seed, rng_ctr=0):
+    """Up to ``fanout`` entries of every row ``seeds[i]`` of ``csr`` (a DeviceCSR) ->
+    DGLMISampleNeighbors, whose header states the counts, the draws and the order.  Returns
+    (offsets int64 (n + 1), nbr int32, eid int64) on the device."""
+    L = _ffi.lib()
+    head = (int(fanout), 1 if replace else 0, int(rng_seed) & (2 ** 64 - 1),
+            int(rng_ctr) & (2 ** 64 - 1))
+    return _two_phase(L.DGLMISampleNeighbors, csr, seeds, head, ())
+
+
+def csr_gather_rows(csr, rows):
+    """Every entry of the rows ``rows[i]`` of ``csr``, row by row in CSR order ->
+    DGLMICsrGatherRows.  Returns (offsets, nbr, eid) like ``sample_neighbors``."""
+    return _two_phase(_ffi.lib().DGLMICsrGatherRows, csr, rows, (), ())
+
+
+def relabel_table(device, num_nodes):
+    """The device's relabel table, grown on demand; all 2^31 - 1 between calls."""
+    device = th.device(device)
+    t = _relabel_tables.get(str(device))
+    if t is None or t.shape[0] < num_nodes:
+        t = th.full((max(int(num_nodes), 1),), _RELABEL_FREE, dtype=th.int32, device=device)
+        _relabel_tables[str(device)] = t
+    return t
+
+
+def block_relabel(dst_nodes, src, num_nodes, include_dst=True, extra=None):
+    """The block ids of ``to_block`` -> DGLMIBlockRelabelMark / Write (header: the order).
+    ``dst_nodes`` (S) and ``src`` (E): device int32 global ids.  Returns (src_nodes int64
+    (num_src), new_src int32 (E), unique_dst): ``unique_dst`` is the number of distinct
+    nodes among ``dst_nodes`` when ``include_dst``, else 0.  One readback; ``extra`` (a
+    device int64 tensor of one value) is read back with it and returned as a fourth item.
+    The device's table is shared: calls on different streams of one device must not overlap."""
+    dev = dst_nodes.device
+    dst_nodes = _ids32(dst_nodes, "dst_nodes", dev)
+    src = _ids32(src, "src", dev)
+    S, E = int(dst_nodes.shape[0]), int(src.shape[0])
+    if S + E >= 2 ** 31:
+        raise DGLError("to_block: %d destinations and %d edges reach 2^31 positions" % (S, E))
+    table = relabel_table(dev, num_nodes)
+    flags = th.empty(S + E, dtype=th.int32, device=dev)
+    src_nodes = th.empty(S + E, dtype=th.int64, device=dev)
+    new_src = th.empty(E, dtype=th.int32, device=dev)
+    counts = th.empty(2, dtype=th.int64, device=dev)
+    L = _ffi.lib()
+    inc = 1 if include_dst else 0
+    try:
+        return _block_relabel(L, dev, table, num_nodes, dst_nodes, S, src, E, inc, flags, src_nodes,
+                              new_src, counts, extra)
+    except Exception:
+        _relabel_tables.pop(str(dev), None)  # it may hold marks: the next call starts afresh
+        raise
+
+
+def _block_relabel(L, dev, table, num_nodes, dst_nodes, S, src, E, inc, flags, src_nodes, new_src,
+                   counts, extra):
+    with th.cuda.device(dev):
+        check_call(L.DGLMIBlockRelabelMark(_vp(table), int(num_nodes), _vp(dst_nodes), S, _vp(src), E,
+                                           inc, _vp(flags), _stream(flags)))
+        scan = th.cumsum(flags, 0, dtype=th.int32)
+        check_call(L.DGLMIBlockRelabelWrite(_vp(table), int(num_nodes), _vp(dst_nodes), S, _vp(src), E,
+                                            inc, _vp(flags), _vp(scan), _vp(src_nodes), _vp(new_src),
+                                            _vp(counts), _stream(flags)))
+        if extra is not None:
+            counts = th.cat([counts, extra])
+        got = [int(v) for v in counts.tolist()]  # the call's one readback
+    if extra is not None:
+        return src_nodes[:got[0]], new_src, got[1], got[2]
+    return src_nodes[:got[0]], new_src, got[1]

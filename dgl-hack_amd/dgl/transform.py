@@ -289,3 +289,182 @@ def segmented_knn_graph(x, k, segs):
     if not isinstance(x, th.Tensor) or x.dim() != 2:
         raise DGLError("segmented_knn_graph: x must be an (N, D) tensor")
     return _knn_graph(x, k, [int(s) for s in segs], "segmented_knn_graph")
+
+
+# ---- frontiers and blocks on the device (transform.py:764-1040, one node type per side) ---
+def _single_relation(g, what):
+    """(index, canonical edge type or None, n_src, n_dst) of a DGLGraph or a graph with one
+    relation; ``index`` has ``get_immutable_gidx``."""
+    from ._ffi import DGLError
+    from .graph import DGLGraph
+    from .heterograph import DGLHeteroGraph
+    if isinstance(g, DGLGraph):
+        n = g.number_of_nodes()
+        return g._graph, None, n, n
+    if isinstance(g, DGLHeteroGraph):
+        if len(g.canonical_etypes) != 1:
+            raise DGLError("%s: the graph has %d edge types; graphs with more than one edge type "
+                           "are not supported" % (what, len(g.canonical_etypes)))
+        rel = g._graph
+        return rel, g.canonical_etypes[0], rel.n_src, rel.n_dst
+    raise DGLError("%s: expected a DGLGraph or a DGLHeteroGraph, got %s" % (what, type(g)))
+
+
+def _built_on(index):
+    """The device a graph was built on, or None for a host-built graph."""
+    pair = getattr(index, "_device_only", None)
+    if pair is not None:
+        return pair[0].device
+    t = getattr(index, "_dev_src", None)
+    return None if t is None else t.device
+
+
+def _device_ids(ids, limit, device, what, name):
+    """``ids`` (tensor or sequence) as a device int32 tensor.  Host ids are range-checked
+    here; device ids are not read (the kernels treat an id outside the range as a node
+    without edges).  ``device``: the graph's device or None.  Returns (ids, device)."""
+    import torch as th
+    from ._ffi import DGLError
+    if isinstance(ids, th.Tensor) and ids.device.type == "cuda":
+        if ids.dtype not in (th.int32, th.int64) or ids.dim() != 1:
+            raise DGLError("%s: %s must be a 1-D int32 or int64 tensor" % (what, name))
+        if device is not None and ids.device != device:
+            raise DGLError("%s: %s is on %s, the graph on %s" % (what, name, ids.device, device))
+        return ids.to(th.int32).contiguous(), ids.device
+    if isinstance(ids, th.Tensor):
+        if ids.is_floating_point() or ids.dtype == th.bool:
+            raise DGLError("%s: %s must hold integers, got %s" % (what, name, ids.dtype))
+        host = ids.detach().numpy().astype(np.int64).reshape(-1)
+    else:
+        host = np.asarray(ids)
+        if host.size and not np.issubdtype(host.dtype, np.integer):
+            raise DGLError("%s: %s must hold integers, got %s" % (what, name, host.dtype))
+        host = host.astype(np.int64).reshape(-1)
+    if host.size and (host.min() < 0 or host.max() >= limit):
+        bad = host[(host < 0) | (host >= limit)][0]
+        raise DGLError("%s: node %d of %s is out of range [0, %d)" % (what, bad, name, limit))
+    if device is None:
+        if not th.cuda.is_available():
+            raise DGLError("%s: no ROCm device: the MI355X engine runs on ROCm devices only" % what)
+        device = th.device("cuda", th.cuda.current_device())
+    return th.from_numpy(host.astype(np.int32)).to(device), device
+
+
+def _edge_graph(g, cetype, src, dst, n_src, n_dst, eid):
+    """A graph of ``g``'s kind and node counts with the given device edges; ``eid`` (device
+    int64 ids into ``g``) goes to ``edata[EID]``.  No CSR is built."""
+    from .base import EID
+    from .graph import DGLGraph
+    from .heterograph import DGLHeteroGraph
+    if cetype is None:
+        out = DGLGraph.from_device_coo(src, dst, n_src)
+    else:
+        out = DGLHeteroGraph.from_device_coo(cetype, src, dst, n_src, n_dst)
+    out.edata[EID] = eid
+    return out
+
+
+def _row_owner(offsets, total):
+    """The slot of every output entry of a two-phase call (device int32)."""
+    from .graph_index import device_expand_rows
+    return device_expand_rows(offsets, total)
+
+
+def _subgraph(g, nodes, inbound, what):
+    from . import kernel as K
+    index, cetype, n_src, n_dst = _single_relation(g, what)
+    ids, dev = _device_ids(nodes, n_dst if inbound else n_src, _built_on(index), what, "nodes")
+    gidx = index.get_immutable_gidx(dev)
+    offsets, nbr, eid = K.csr_gather_rows(gidx.in_csr if inbound else gidx.out_csr, ids)
+    own = ids[_row_owner(offsets, int(nbr.shape[0])).long()]
+    src, dst = (nbr, own) if inbound else (own, nbr)
+    return _edge_graph(g, cetype, src, dst, n_src, n_dst, eid)
+
+
+def in_subgraph(g, nodes):
+    """The graph of ``g``'s nodes that keeps only the edges into ``nodes``
+    (``transform.py:968-1005``): node by node in the order given, a node's edges in in-CSR
+    order (sources ascending).  ``edata[dgl.EID]`` holds their ids in ``g`` (device int64).
+    Built by one device gather balanced over the output (``dgl.kernel.csr_gather_rows``); no id
+    visits the host."""
+    return _subgraph(g, nodes, True, "in_subgraph")
+
+
+def out_subgraph(g, nodes):
+    """:func:`in_subgraph` for the edges out of ``nodes`` (``transform.py:1007-1044``)."""
+    return _subgraph(g, nodes, False, "out_subgraph")
+
+
+def to_block(g, dst_nodes=None, include_dst_in_src=True):
+    """The bipartite block of the edges of ``g`` into ``dst_nodes`` (``transform.py:764-921``
+    for one node type per side).  Edges are ordered by destination, in the order given, then
+    by in-CSR position.  The destination ``dst_nodes[j]`` is node j of the DST side; with
+    ``include_dst_in_src`` it is node j of the SRC side too, and the other sources follow by
+    first appearance, so ``X[:block.number_of_dst_nodes()]`` are the destinations' rows of a
+    SRC-side feature ``X``.  On a graph whose two sides differ in type (``dgl.bipartite``)
+    the destinations are never among the sources.  ``srcdata[dgl.NID]``,
+    ``dstdata[dgl.NID]`` and ``edata[dgl.EID]`` are device int64 ids into ``g``.  The node
+    types of the block are ``'SRC/' + utype`` and ``'DST/' + vtype``.
+
+    ``dst_nodes`` None: every node with an in-edge, ascending.  Repeated ``dst_nodes``
+    raise.  When ``g`` is the result of ``dgl.sampling.sample_neighbors(..., edge_dir='in')``
+    and ``dst_nodes`` are its seeds, the frontier's edge list already is that order and no
+    CSR of the frontier is built.  One size is read back; no id visits the host."""
+    import torch as th
+    from . import kernel as K
+    from ._ffi import DGLError
+    from .base import NID, EID
+    from .heterograph import DGLHeteroGraph
+    what = "to_block"
+    index, cetype, n_src, n_dst = _single_relation(g, what)
+    utype, etype, vtype = ("_N", "_E", "_N") if cetype is None else cetype
+    if isinstance(dst_nodes, dict):
+        if list(dst_nodes.keys()) != [vtype]:
+            raise DGLError("to_block: dst_nodes must be given for node type %s alone" % vtype)
+        dst_nodes = dst_nodes[vtype]
+    include = bool(include_dst_in_src) and utype == vtype
+    built_on = _built_on(index)
+    if dst_nodes is None:
+        if built_on is None and not th.cuda.is_available():
+            raise DGLError("to_block: no ROCm device: the MI355X engine runs on ROCm devices only")
+        dev = built_on if built_on is not None else th.device("cuda", th.cuda.current_device())
+        deg = index.get_immutable_gidx(dev).in_csr.degrees()
+        ids = th.nonzero(deg > 0).reshape(-1).to(th.int32)
+    else:
+        ids, dev = _device_ids(dst_nodes, n_dst, built_on, what, "dst_nodes")
+    S = int(ids.shape[0])
+
+    info = getattr(g, "_sampled", None)
+    fast = (info is not None and info["edge_dir"] == "in" and info["seeds"].device == dev and
+            int(info["seeds"].shape[0]) == S and include)
+    if fast:
+        # the frontier's own edge list, if the destinations are its seeds: decided on the
+        # device and read back with the relabel's sizes
+        src = index._device_only[0] if cetype is None else index._dev_src
+        differs = (info["seeds"] != ids).any().reshape(1).long()
+        src_nodes, new_src, uniq, differs = K.block_relabel(ids, src, n_src, True, extra=differs)
+        if differs:
+            fast = False
+        else:
+            if uniq != S:
+                raise DGLError("to_block: dst_nodes repeats a node (%d distinct of %d)" % (uniq, S))
+            E = int(src.shape[0])
+            new_dst = _row_owner(info["offsets"], E)
+            eid = th.arange(E, dtype=th.int64, device=dev)
+    if not fast:
+        gidx = index.get_immutable_gidx(dev)
+        offsets, src, eid = K.csr_gather_rows(gidx.in_csr, ids)
+        if not include:
+            uniq = K.block_relabel(ids, src[:0], n_dst, True)[2]
+            if uniq != S:
+                raise DGLError("to_block: dst_nodes repeats a node (%d distinct of %d)" % (uniq, S))
+        src_nodes, new_src, uniq = K.block_relabel(ids, src, n_src, include)
+        if include and uniq != S:
+            raise DGLError("to_block: dst_nodes repeats a node (%d distinct of %d)" % (uniq, S))
+        new_dst = _row_owner(offsets, int(src.shape[0]))
+    block = DGLHeteroGraph.from_device_coo(("SRC/" + utype, etype, "DST/" + vtype), new_src, new_dst,
+                                           int(src_nodes.shape[0]), S)
+    block.srcdata[NID] = src_nodes
+    block.dstdata[NID] = ids.long()
+    block.edata[EID] = eid
+    return block

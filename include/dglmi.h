@@ -828,6 +828,92 @@ int DGLMIKnnTile(int64_t D, int32_t k, int32_t* query_rows, int32_t* cand_rows,
 int DGLMIKnnSelect(const DGLMISegments* seg, const DGLMIArray* x, int32_t k, int32_t* nbr,
                    float* dist, void* stream);
 
+/* ---- neighbour sampling, row gathers, block relabelling ----------------------
+ * dgl.sampling.sample_neighbors, dgl.in_subgraph / out_subgraph and dgl.to_block
+ * (_CAPI_DGLSampleNeighbors, _CAPI_DGLInSubgraph, _CAPI_DGLToBlock) with every node and
+ * edge id kept on the device.
+ *
+ * Common arguments.  csr: one direction of a graph -- the in-CSR for edge_dir 'in' (a
+ *   row's entries are its predecessors), the out-CSR for 'out'; `rows` of the CSR is not
+ *   read.  num_bits: 32, or 64 when csr->indptr / csr->data hold int64 values.  seeds /
+ *   rows: device int32 row ids, which may repeat and come in any order; an id outside
+ *   [0, csr->num_rows) counts as a row of degree 0.  offsets: num + 1 device int64 values.
+ *   out_nbr: device int32, the CSR `indices` of the picks; out_eid: device int64, the CSR
+ *   `data` of the picks (parent edge ids).  A row's degree must be below 2^32.
+ *
+ * Every entry has two phases, chosen by out_nbr.  out_nbr == NULL is the count phase: it
+ *   writes offsets[0] = 0 and offsets[i + 1] = cnt[i].  The caller turns `offsets` into its
+ *   running sum (so that offsets[i] is the exclusive scan of cnt and offsets[num] the
+ *   number of picks, the only value the host reads back), allocates num_out = offsets[num]
+ *   entries of out_nbr / out_eid and calls again with them: the pick phase, which reads
+ *   `offsets` and writes the picks of slot i at offsets[i] .. offsets[i + 1] - 1.  Writes
+ *   outside [0, num_out) are dropped.
+ *
+ * DGLMISampleNeighbors (rowwise_pick.h:68-110 without the -1 padding).  With deg the
+ *   degree of seeds[i]:
+ *     cnt[i] = 0                 when deg = 0,
+ *     cnt[i] = fanout            when deg > 0 and replace != 0,
+ *     cnt[i] = min(deg, fanout)  when deg > 0 and replace == 0.
+ *   The picks are positions 0 .. deg - 1 inside the row, listed in ascending position (so
+ *   a seed's `indices` ascend when the row's do, and repeats under replacement are
+ *   adjacent).  They are a function of (csr, seeds, fanout, replace, rng_seed, rng_ctr)
+ *   alone.  Draw t of seed slot i, r(i, t), is a 32-bit value: component t & 3 (x, y, z, w)
+ *   of Philox4x32-10 with the counter (lo32(c), hi32(c), lo32(i), hi32(i)), c = rng_ctr +
+ *   (t >> 2) mod 2^64, and the key (lo32(rng_seed), hi32(rng_seed)).  mulhi(r, n) is
+ *   floor(r * n / 2^32).
+ *     - replace != 0: pick t is mulhi(r(i, t), deg), t = 0 .. fanout - 1; then sorted.
+ *       Position p is hit by floor(2^32 / deg) or by ceil(2^32 / deg) of the 2^32 values
+ *       of r: its probability differs from 1 / deg by less than deg / 2^32 in relative
+ *       terms (1.2e-6 at deg = 5,000).
+ *     - replace == 0, deg <= fanout: the whole row in CSR order.
+ *     - replace == 0, deg > fanout: Floyd's subset algorithm.  For t = 0 .. fanout - 1 in
+ *       this order: j = deg - fanout + t, p = mulhi(r(i, t), j + 1), and p = j when p is
+ *       among the picks of steps 0 .. t - 1; p is the pick of step t.  Then sorted.  Every
+ *       subset has the same probability up to the same bias; the cost is O(fanout) per
+ *       seed whatever the degree.
+ *   0 <= fanout <= DGLMISampleMaxFanout() (64: a seed's picks are held across the lanes of
+ *   one group of lanes, at most a wavefront); fanout == 0 gives cnt = 0 everywhere.
+ *   No atomics and no float arithmetic take part: the same bits on every run.
+ *
+ * DGLMICsrGatherRows: the take-all case for any degree.  cnt[i] = deg of rows[i]; the entries
+ *   of rows[i] in CSR order.  One lane per output entry, so a hub row does not serialise.
+ *
+ * DGLMIBlockRelabelMark / DGLMIBlockRelabelWrite: the IdHashMap ordering of
+ *   to_bipartite.cc:39-56 for one node type, without a hash table and without a sort.
+ *   Positions 0 .. S + E - 1: position j < S is dst_nodes[j] (left out when include_dst
+ *   is 0), position S + e is src[e], the source of edge e (device int32 global ids; an id
+ *   outside [0, num_nodes) is left out and relabels to -1).  A node's owner is its lowest
+ *   position.  The new id of a node is the number of owners at lower positions than its
+ *   own: with include_dst the destinations keep 0 .. S - 1 in the order given (if they
+ *   are unique) and new sources follow by first appearance.
+ *   table: device int32, num_nodes entries, caller-owned and all INT32_MAX on entry; it
+ *   is all INT32_MAX again when Write has run (Write stores the value back into exactly
+ *   the entries Mark lowered).  S + E < 2^31.
+ *     Mark: table[v] = min over the positions of v (an integer atomic minimum: the result
+ *       does not depend on the order of arrival); flags[p] = 1 when p owns its node, else
+ *       0 (S + E device int32).
+ *     The caller computes scan = the inclusive running sum of flags (device int32).
+ *     Write: src_nodes[id] = the global id of new source id (device int64, room for
+ *       S + E); new_src[e] = the new id of src[e] (device int32); counts[0] = the number
+ *       of source nodes, counts[1] = the number of owners among positions 0 .. S - 1
+ *       (device int64[2], one readback; counts[1] < S with include_dst means a repeated
+ *       destination). */
+int32_t DGLMISampleMaxFanout(void);
+int DGLMISampleNeighbors(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds,
+                         int64_t num_seeds, int32_t fanout, int32_t replace, uint64_t rng_seed,
+                         uint64_t rng_ctr, int64_t* offsets, int64_t num_out, int32_t* out_nbr,
+                         int64_t* out_eid, void* stream);
+int DGLMICsrGatherRows(const DGLMICsr* csr, int32_t num_bits, const int32_t* rows, int64_t num_rows,
+                    int64_t* offsets, int64_t num_out, int32_t* out_nbr, int64_t* out_eid,
+                    void* stream);
+int DGLMIBlockRelabelMark(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                          const int32_t* src, int64_t E, int32_t include_dst, int32_t* flags,
+                          void* stream);
+int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
+                           const int32_t* src, int64_t E, int32_t include_dst, const int32_t* flags,
+                           const int32_t* scan, int64_t* src_nodes, int32_t* new_src,
+                           int64_t* counts, void* stream);
+
 /* ---- measurement utility (bench.py; no reference counterpart) -------------
  * dst[i] = src[i] for num_floats fp32 values (a multiple of 4, both 16-B aligned)
  * by a float4 streaming copy: the access pattern MI355X_MICROARCH.md quotes the
