@@ -3031,4 +3031,100 @@ int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst
   API_END();
 }
 
+// ---- random walks and visit counts (kernels_walk.hip) ---------------------------------
+int32_t DGLMIWalkMaxRelations(void) { return walk_max_relations(); }
+int32_t DGLMIWalkStageChunk(void) { return walk_stage_chunk(); }
+
+int DGLMIRandomWalk(const DGLMICsr* const* csrs, const int32_t* num_bits, int32_t num_rels,
+                    const int32_t* metapath, int64_t L, const int32_t* seeds, int64_t num_walks,
+                    const uint64_t* restart, uint64_t rng_seed, uint64_t rng_ctr, int32_t variant,
+                    int64_t* traces, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(num_rels >= 1 && num_rels <= walk_max_relations(),
+              "random walk: the number of relations must be between 1 and " +
+                  std::to_string(walk_max_relations()) + ", got " + std::to_string(num_rels));
+  DGLMI_CHECK(csrs != nullptr && num_bits != nullptr, "null relation table");
+  DGLMI_CHECK(L >= 0 && L < (int64_t(1) << 31), "random walk: bad walk length");
+  DGLMI_CHECK(num_walks >= 0 && num_walks < (int64_t(1) << 31), "random walk: bad walk count");
+  DGLMI_CHECK(variant >= 0 && variant <= 2, "random walk: variant must be 0, 1 or 2");
+  WalkTable tab{};
+  tab.num_rels = num_rels;
+  for (int r = 0; r < num_rels; ++r) {
+    const SampleCsr c = sample_csr(csrs[r], num_bits[r]);
+    tab.rel[r] = WalkRel{c.indptr.p, c.indices, c.num_rows, c.indptr.wide};
+  }
+  if (num_walks == 0) return 0;
+  DGLMI_CHECK(seeds != nullptr, "null seeds");
+  DGLMI_CHECK(traces != nullptr, "null traces");
+  DGLMI_CHECK(L == 0 || num_rels == 1 || metapath != nullptr, "null metapath");
+  DeviceGuard guard(device_of(traces, "random walk traces: not a device pointer"));
+  const bool staged = variant != 1;  // the shipped choice: DESIGN 4.12 has the A/B
+  launch_walk(tab, metapath, L, seeds, num_walks, restart, rng_seed, rng_ctr, staged, traces,
+              static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "random walk launch");
+  API_END();
+}
+
+int32_t DGLMIVisitMaxK(void) { return visit_max_k(); }
+int32_t DGLMIVisitMaxWidth(void) { return visit_max_width(); }
+
+namespace {
+
+// the candidate columns col0, col0 + col_step, .. < row_len, or throws
+int64_t visit_columns(int64_t row_len, int64_t col0, int64_t col_step) {
+  DGLMI_CHECK(row_len >= 1, "visit top-k: rows need at least one entry");
+  DGLMI_CHECK(col0 >= 0 && col_step >= 1, "visit top-k: col0 must not be negative and col_step "
+                                          "must be at least 1");
+  return col0 < row_len ? (row_len - col0 + col_step - 1) / col_step : 0;
+}
+
+void visit_check_k(int32_t K) {
+  DGLMI_CHECK(K >= 1 && K <= visit_max_k(), "visit top-k: K must be between 1 and " +
+                                                std::to_string(visit_max_k()) + ", got " +
+                                                std::to_string(K));
+}
+
+void visit_check_width(int64_t W) {
+  DGLMI_CHECK(W >= 1 && W <= visit_max_width(),
+              "visit top-k: a seed needs between 1 and " + std::to_string(visit_max_width()) +
+                  " candidates (walks per seed x columns), got " + std::to_string(W));
+}
+
+}  // namespace
+
+int DGLMIVisitTile(int64_t W, int32_t K, int32_t* padded_width, int32_t* seeds_per_workgroup) {
+  API_BEGIN();
+  DGLMI_CHECK(padded_width && seeds_per_workgroup, "null argument");
+  visit_check_k(K);
+  visit_check_width(W);
+  int p = 0, s = 0;
+  visit_tile(W, &p, &s);
+  *padded_width = p;
+  *seeds_per_workgroup = s;
+  API_END();
+}
+
+int DGLMIVisitTopK(const int64_t* traces, int64_t row_len, int64_t num_seeds,
+                   int64_t walks_per_seed, int64_t col0, int64_t col_step, int32_t K,
+                   int32_t* out_nbr, int32_t* out_cnt, int32_t* out_num, void* stream) {
+  API_BEGIN();
+  visit_check_k(K);
+  const int64_t ncols = visit_columns(row_len, col0, col_step);
+  DGLMI_CHECK(walks_per_seed >= 0 && walks_per_seed <= visit_max_width(),
+              "visit top-k: walks per seed must be between 0 and " +
+                  std::to_string(visit_max_width()) + ", got " + std::to_string(walks_per_seed));
+  visit_check_width(walks_per_seed * ncols);
+  DGLMI_CHECK(num_seeds >= 0 && num_seeds * static_cast<int64_t>(K) < (int64_t(1) << 31),
+              "visit top-k: num_seeds * K must stay below 2^31");
+  if (num_seeds == 0) return 0;
+  DGLMI_CHECK(traces != nullptr, "null traces");
+  DGLMI_CHECK(out_nbr != nullptr && out_cnt != nullptr && out_num != nullptr, "null output");
+  DeviceGuard guard(device_of(out_num, "visit top-k out_num: not a device pointer"));
+  launch_visit_topk(traces, row_len, num_seeds, walks_per_seed, col0, col_step,
+                    static_cast<int>(ncols), K, out_nbr, out_cnt, out_num,
+                    static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "visit top-k launch");
+  API_END();
+}
+
 }  // extern "C"

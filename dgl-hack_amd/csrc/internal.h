@@ -804,4 +804,31 @@ void launch_relabel_write(int32_t* table, int64_t num_nodes, const int32_t* dst_
                           const int32_t* scan, int64_t* src_nodes, int32_t* new_src, int64_t* counts,
                           hipStream_t s);
 
+// random walks and visit counts (kernels_walk.hip): see DGLMIRandomWalk and DGLMIVisitTopK.
+// The relations' out-CSRs travel by value in the kernel argument: no device allocation.
+constexpr int kWalkMaxRels = 16;
+struct WalkRel {
+  const void* indptr;      // num_rows + 1 (int64 values when wide)
+  const int32_t* indices;
+  int64_t num_rows;
+  int wide;
+};
+struct WalkTable {
+  int num_rels;
+  WalkRel rel[kWalkMaxRels];
+};
+int walk_max_relations();
+int walk_stage_chunk();  // columns per flush of the staged variant
+void launch_walk(const WalkTable& tab, const int32_t* metapath, int64_t L, const int32_t* seeds,
+                 int64_t num_walks, const uint64_t* restart, uint64_t rng_seed, uint64_t rng_ctr,
+                 bool staged, int64_t* traces, hipStream_t s);
+int visit_max_k();
+int visit_max_width();
+void visit_tile(int64_t W, int* padded, int* seeds_per_wg);
+// ncols: the candidate columns col0, col0 + col_step, .. < row_len; walks_per_seed * ncols
+// is at most visit_max_width()
+void launch_visit_topk(const int64_t* traces, int64_t row_len, int64_t num_seeds,
+                       int64_t walks_per_seed, int64_t col0, int64_t col_step, int ncols, int K,
+                       int32_t* out_nbr, int32_t* out_cnt, int32_t* out_num, hipStream_t s);
+
 }  // namespace dglmi

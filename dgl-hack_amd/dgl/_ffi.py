@@ -420,6 +420,21 @@ _SIGS = {
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMIWalkMaxRelations": (ctypes.c_int32, []),
+    "DGLMIWalkStageChunk": (ctypes.c_int32, []),
+    "DGLMIRandomWalk": (ctypes.c_int, [
+        ctypes.POINTER(ctypes.POINTER(CSR)), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMIVisitMaxK": (ctypes.c_int32, []),
+    "DGLMIVisitMaxWidth": (ctypes.c_int32, []),
+    "DGLMIVisitTile": (ctypes.c_int, [
+        ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+        ctypes.POINTER(ctypes.c_int32)]),
+    "DGLMIVisitTopK": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -9,6 +9,7 @@ and overwritten completely, exactly like the reference's
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1364,3 +1365,101 @@ def _block_relabel(L, dev, table, num_nodes, dst_nodes, S, src, E, inc, flags, s
     if extra is not None:
         return src_nodes[:got[0]], new_src, got[1], got[2]
     return src_nodes[:got[0]], new_src, got[1]
+
+
+# ---- random walks and visit counts (dgl.sampling.random_walk, PinSAGESampler) -------------
+def walk_max_relations():
+    """The most relations one ``random_walk`` call takes (DGLMIWalkMaxRelations)."""
+    return int(_ffi.lib().DGLMIWalkMaxRelations())
+
+
+def walk_stage_chunk():
+    """Columns per flush of the walk kernel's staged stores (DGLMIWalkStageChunk)."""
+    return int(_ffi.lib().DGLMIWalkStageChunk())
+
+
+def visit_max_k():
+    """The largest K of ``visit_topk`` (DGLMIVisitMaxK)."""
+    return int(_ffi.lib().DGLMIVisitMaxK())
+
+
+def visit_max_width():
+    """The most candidates (walks per seed x columns) of one seed of ``visit_topk``
+    (DGLMIVisitMaxWidth)."""
+    return int(_ffi.lib().DGLMIVisitMaxWidth())
+
+
+def visit_tile(W, K):
+    """(padded width, seed slots per workgroup) of the kernel instance that serves ``W``
+    candidates per seed at ``K`` (DGLMIVisitTile)."""
+    p, s = ctypes.c_int32(), ctypes.c_int32()
+    check_call(_ffi.lib().DGLMIVisitTile(int(W), int(K), ctypes.byref(p), ctypes.byref(s)))
+    return p.value, s.value
+
+
+def restart_thresholds(probs):
+    """The 64-bit thresholds of DGLMIRandomWalk for stopping probabilities ``probs`` (floats):
+    min(2^32, floor(p 2^32)) from p as a double, as a list of ints."""
+    return [2 ** 32 if float(p) >= 1.0 else int(math.floor(float(p) * 4294967296.0)) for p in probs]
+
+
+def random_walk(csrs, metapath, seeds, restart, rng_seed, rng_ctr=0, variant=0):
+    """Uniform random walks -> DGLMIRandomWalk, whose header states the steps and the draws.
+    ``csrs``: the relations' out-CSRs (DeviceCSR), at most ``walk_max_relations()``;
+    ``metapath``: device int32 (L) indices into ``csrs``; ``seeds``: device int32;
+    ``restart``: device int64 (L) holding the thresholds of ``restart_thresholds``, or None.
+    ``variant``: 0 the shipped store path, 1 per-lane stores, 2 staged stores (the same
+    traces).  Returns ``traces``, device int64 (len(seeds), L + 1)."""
+    csrs = list(csrs)
+    if not 1 <= len(csrs) <= walk_max_relations():
+        raise DGLError("random_walk: %d relations; the kernel takes between 1 and %d"
+                       % (len(csrs), walk_max_relations()))
+    dev = csrs[0].indptr.device
+    seeds = _ids32(seeds, "seeds", dev)
+    metapath = _ids32(metapath, "metapath", dev)
+    L = int(metapath.shape[0])
+    if restart is not None:
+        if (not isinstance(restart, th.Tensor) or restart.dtype != th.int64 or restart.device != dev
+                or restart.dim() != 1 or int(restart.shape[0]) != L):
+            raise DGLError("restart must be a 1-D int64 tensor of %d thresholds on %s" % (L, dev))
+        restart = restart.contiguous()
+    for c in csrs:
+        if c.indptr.device != dev:
+            raise DGLError("random_walk: the relations' CSRs are on different devices")
+    cs = [c.cstruct() for c in csrs]
+    table = (ctypes.POINTER(_ffi.CSR) * len(cs))(*[ctypes.pointer(c) for c in cs])
+    bits = (ctypes.c_int32 * len(cs))(*[c.bits for c in csrs])
+    n = int(seeds.shape[0])
+    traces = th.empty((n, L + 1), dtype=th.int64, device=dev)
+    with th.cuda.device(dev):
+        check_call(_ffi.lib().DGLMIRandomWalk(
+            table, bits, len(cs), _vp(metapath), L, _vp(seeds), n, _vp(restart),
+            int(rng_seed) & (2 ** 64 - 1), int(rng_ctr) & (2 ** 64 - 1), int(variant), _vp(traces),
+            _stream(traces)))
+    return traces
+
+
+def visit_topk(traces, walks_per_seed, col0, col_step, k):
+    """Per seed slot, the ``k`` most visited nodes of its walks -> DGLMIVisitTopK (header: the
+    candidates, the order and the limits).  ``traces``: device int64 (num_seeds *
+    walks_per_seed, row_len).  Returns (nbr int32 (num_seeds, k), cnt int32 (num_seeds, k),
+    num int32 (num_seeds)) on the device; unused entries are -1 / 0."""
+    if (not isinstance(traces, th.Tensor) or traces.dtype != th.int64 or traces.dim() != 2
+            or traces.device.type != "cuda"):
+        raise DGLError("traces must be a 2-D int64 tensor on a ROCm device")
+    traces = traces.contiguous()
+    walks_per_seed, k = int(walks_per_seed), int(k)
+    rows, row_len = int(traces.shape[0]), int(traces.shape[1])
+    if walks_per_seed < 1 or rows % walks_per_seed:
+        raise DGLError("visit_topk: %d rows are not a multiple of %d walks per seed"
+                       % (rows, walks_per_seed))
+    n = rows // walks_per_seed
+    dev = traces.device
+    nbr = th.empty((n, max(k, 0)), dtype=th.int32, device=dev)
+    cnt = th.empty((n, max(k, 0)), dtype=th.int32, device=dev)
+    num = th.empty(n, dtype=th.int32, device=dev)
+    with th.cuda.device(dev):
+        check_call(_ffi.lib().DGLMIVisitTopK(
+            _vp(traces), row_len, n, walks_per_seed, int(col0), int(col_step), k, _vp(nbr), _vp(cnt),
+            _vp(num), _stream(traces)))
+    return nbr, cnt, num

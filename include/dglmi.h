@@ -914,6 +914,77 @@ int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst
                            const int32_t* scan, int64_t* src_nodes, int32_t* new_src,
                            int64_t* counts, void* stream);
 
+/* ---- random walks and visit counts ------------------------------------------
+ * dgl.sampling.random_walk and the counting step of RandomWalkNeighborSampler /
+ * PinSAGESampler (_CAPI_DGLSamplingRandomWalk, ..WithRestart, ..WithStepwiseRestart;
+ * pinsage.py:103-117) with every node id kept on the device.
+ *
+ * DGLMIRandomWalk (randomwalks_cpu.h:47-61, metapath_randomwalk.h:61-98, uniform picks).
+ *   csrs: a host array of num_rels pointers to out-CSRs (a row's entries are the row node's
+ *     successors under that relation; only indptr, indices and num_rows are read), with
+ *     num_bits[r] = 32, or 64 when csrs[r]->indptr holds int64 values.  1 <= num_rels <=
+ *     DGLMIWalkMaxRelations() (16).  The table is copied into the kernel argument: the call
+ *     makes no device allocation and no copy.
+ *   metapath: device int32, L entries, the relation (index into csrs) of every step; L >= 0.
+ *     It is not read when num_rels == 1 (every step takes relation 0; it may be NULL).  An
+ *     entry outside [0, num_rels) makes the step a dead end.
+ *   seeds: device int32, num_walks entries (0 <= num_walks < 2^31), which may repeat.
+ *   restart: device uint64, L thresholds, or NULL (no restarts).
+ *   traces: device int64, num_walks x (L + 1), row-major.
+ * Walk i:
+ *   1. traces[i][0] = seeds[i].
+ *   2. Step t = 0 .. L - 1 from the current node v (v = seeds[i] at t = 0): deg is the
+ *      length of row v of relation metapath[t], and 0 when v is outside [0, num_rows) of
+ *      that relation.
+ *   3. deg == 0: traces[i][t + 1 ..] = -1 and the walk ends.
+ *   4. Otherwise the next node is indices[indptr[v] + mulhi(x, deg)]; it is written to
+ *      traces[i][t + 1].
+ *   5. Then, if restart != NULL and y < restart[t] (both as 64-bit values): traces[i][t + 2
+ *      ..] = -1 and the walk ends.
+ * Draws.  (x, y, z, w) is Philox4x32-10 with the counter (lo32(c), hi32(c), lo32(i),
+ *   hi32(i)), c = rng_ctr + t mod 2^64, and the key (lo32(rng_seed), hi32(rng_seed)); z and
+ *   w are unused.  mulhi(r, n) = floor(r * n / 2^32); a row's degree must be below 2^32.
+ *   Entry p of a row is hit by floor(2^32 / deg) or ceil(2^32 / deg) of the 2^32 values of x
+ *   (the bias of DGLMISampleNeighbors).  The traces are a function of the arguments alone:
+ *   no atomics, no float arithmetic, the same bits on every run and for every variant.
+ * Restart thresholds.  The caller computes restart[t] = min(2^32, floor(p_t * 2^32)) from
+ *   the probability p_t as a double: y < restart[t] holds for exactly restart[t] of the 2^32
+ *   values of y, so p = 0 never stops, p >= 1 always stops, and the probability is quantised
+ *   to multiples of 2^-32 (rounded down: p = 2^-33 never stops).
+ * variant: 0 = the shipped choice; 1 = every lane stores its own row (8 bytes at a stride of
+ *   (L + 1) * 8); 2 = DGLMIWalkStageChunk() (8) columns of a wavefront's 64 rows are staged
+ *   in LDS and flushed row by row.  The variants differ in speed only.
+ *
+ * DGLMIVisitTopK: to_simple(return_counts) + select_topk + gather for one seed's walks, as
+ *   one kernel that reads the traces in place.
+ *   traces: device int64 rows of row_len entries.  Seed slot s (0 <= s < num_seeds) owns rows
+ *   s * walks_per_seed .. (s + 1) * walks_per_seed - 1; its candidates are the entries of
+ *   those rows at the columns col0, col0 + col_step, .. < row_len (col0 >= 0, col_step >= 1),
+ *   W = walks_per_seed * (the number of such columns) of them.  Entries outside [0, 2^31 - 1)
+ *   -- the -1 padding above all -- are ignored.
+ *   out_nbr, out_cnt: device int32, num_seeds x K; out_num: device int32, num_seeds.  The
+ *   distinct candidate ids of slot s are ordered by the number of times they occur,
+ *   descending, then by id ascending (a strict total order); out_num[s] = min(K, distinct),
+ *   the first out_num[s] ids and their counts fill the head of row s of out_nbr / out_cnt,
+ *   and the rest of the row is nbr = -1, cnt = 0.  No atomics: the same bits on every run.
+ *   Limits: 1 <= K <= DGLMIVisitMaxK() (64), 1 <= W <= DGLMIVisitMaxWidth() (4096),
+ *   num_seeds * K < 2^31; otherwise -1 with a message.
+ * DGLMIVisitTile: the shipped instance for W candidates at K -- the padded width (the power
+ *   of two the slot is sorted at, >= 64) and the seed slots one workgroup serves; tests build
+ *   their shapes around these.  Returns -1 for W or K outside the limits. */
+int32_t DGLMIWalkMaxRelations(void);
+int32_t DGLMIWalkStageChunk(void);
+int DGLMIRandomWalk(const DGLMICsr* const* csrs, const int32_t* num_bits, int32_t num_rels,
+                    const int32_t* metapath, int64_t L, const int32_t* seeds, int64_t num_walks,
+                    const uint64_t* restart, uint64_t rng_seed, uint64_t rng_ctr, int32_t variant,
+                    int64_t* traces, void* stream);
+int32_t DGLMIVisitMaxK(void);
+int32_t DGLMIVisitMaxWidth(void);
+int DGLMIVisitTile(int64_t W, int32_t K, int32_t* padded_width, int32_t* seeds_per_workgroup);
+int DGLMIVisitTopK(const int64_t* traces, int64_t row_len, int64_t num_seeds,
+                   int64_t walks_per_seed, int64_t col0, int64_t col_step, int32_t K,
+                   int32_t* out_nbr, int32_t* out_cnt, int32_t* out_num, void* stream);
+
 /* ---- measurement utility (bench.py; no reference counterpart) -------------
  * dst[i] = src[i] for num_floats fp32 values (a multiple of 4, both 16-B aligned)
  * by a float4 streaming copy: the access pattern MI355X_MICROARCH.md quotes the
