@@ -2455,6 +2455,22 @@ int DGLMIRgcnLayer1BackwardEx(const DGLMIGraph* graph,
                                    grad_hidden, grad_weight, grad_loop_weight, stream);
 }
 
+// The dispatch of the layer-1 products and fused walks (hack_kernels.hip), for tests
+// and probes: the rules the launchers themselves call, no device work.
+int64_t DGLMIRgcnGemmSplits(int64_t m, int64_t n, int64_t k) { return dglmi::gemm_splits(m, n, k); }
+
+int DGLMIRgcnGemmInstance(int64_t m, int64_t n, int64_t k, int64_t a_rs, int64_t a_cs,
+                          int64_t b_rs, int64_t b_cs, int a_aligned16, int b_aligned16,
+                          int64_t splits) {
+  return dglmi::gemm_instance(m, n, k, a_rs, a_cs, b_rs, b_cs, a_aligned16 != 0, b_aligned16 != 0,
+                              splits);
+}
+
+int DGLMIRgcnFusedInstance(int64_t gathered_w, int64_t out_w, int64_t rels_incl_loop,
+                           int64_t num_rows, int64_t t_rows) {
+  return dglmi::rgcn_fused_instance(gathered_w, out_w, rels_incl_loop, num_rows, t_rows);
+}
+
 int DGLMIRgcnPrepare(const DGLMIGraph* graph, const DGLMIArray* norm,
                      int32_t num_rels, int32_t layers, DGLMIRgcnState* state, void* stream) {
   API_BEGIN();

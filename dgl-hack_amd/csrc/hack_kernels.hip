@@ -858,6 +858,55 @@ int64_t gemm_splits(int64_t M, int64_t N, int64_t K) {
   return splits;
 }
 
+// ---------------------------------------------------------------------------
+// The dispatch rules, as plain host functions: the launchers below and the queries of
+// the C ABI (DGLMIRgcnGemmInstance / DGLMIRgcnFusedInstance) both call them.
+
+// k_gemm's reduction range per grid z for `splits` requested splits (whole 32-deep
+// slices); launch_gemm then runs (K + k_split - 1) / k_split of them
+int64_t gemm_k_split(int64_t K, int64_t splits) {
+  return ((K + splits - 1) / splits + kTK - 1) / kTK * kTK;
+}
+
+// k_gemm_rows when A is row-major with float4-loadable rows and B fits the LDS of one
+// of the instances; GEMM_GENERIC = not taken
+int gemm_rows_instance(int64_t M, int64_t N, int64_t K, int64_t a_rs, int64_t a_cs,
+                       bool a_aligned16) {
+  if (a_cs != 1 || a_rs % 4 != 0 || K % 4 != 0 || !a_aligned16 || M < 4096) return GEMM_GENERIC;
+  if (N <= 256 && K <= 64) return GEMM_ROWS_8_64;
+  if (N <= 128 && K <= 128) return GEMM_ROWS_4_128;
+  if (N <= 64 && K <= 256) return GEMM_ROWS_2_256;
+  return GEMM_GENERIC;
+}
+
+// k_gemm_tn for C = A^T B with A (K x M) and B (K x N) row-major (a_rs == 1, b_cs == 1),
+// K the long dimension, through the caller's `splits` partial buffers
+int gemm_tn_instance(int64_t M, int64_t N, int64_t K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                     int64_t b_cs, bool a_aligned16, bool b_aligned16, int64_t splits) {
+  if (a_rs != 1 || b_cs != 1 || splits < 2 || K < 4096) return GEMM_GENERIC;
+  if (M % 4 != 0 || N % 4 != 0 || a_cs % 4 != 0 || b_rs % 4 != 0 || !a_aligned16 || !b_aligned16)
+    return GEMM_GENERIC;
+  if (M <= 64 && N <= 256) return GEMM_TN_2_8;
+  if (M <= 64 && N <= 320) return GEMM_TN_2_10;
+  if (M <= 128 && N <= 128) return GEMM_TN_4_4;
+  if (M <= 256 && N <= 64) return GEMM_TN_8_2;
+  return GEMM_GENERIC;
+}
+
+int gemm_instance(int64_t M, int64_t N, int64_t K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                  int64_t b_cs, bool a_aligned16, bool b_aligned16, int64_t splits) {
+  if (M <= 0 || N <= 0 || K <= 0) return GEMM_NONE;
+  if (const int i = gemm_rows_instance(M, N, K, a_rs, a_cs, a_aligned16)) return i;
+  return gemm_tn_instance(M, N, K, a_rs, a_cs, b_rs, b_cs, a_aligned16, b_aligned16, splits);
+}
+
+// k_gemm_tn's launch: rows of the long dimension per block (whole 32-row slices) for at
+// most `max_blocks` (and 512) blocks; (R + rows - 1) / rows blocks then run
+int64_t gemm_tn_rows_per_block(int64_t R, int64_t max_blocks) {
+  const int64_t nb = max_blocks < 512 ? max_blocks : 512;
+  return ((R + nb - 1) / nb + kSlice - 1) / kSlice * kSlice;
+}
+
 namespace {
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -872,44 +921,15 @@ void launch_rows(const float* A, int64_t lda, const float* B, int64_t b_rs, int6
                      b_cs, C, M, static_cast<int>(N), static_cast<int>(K));
 }
 
-// k_gemm_rows when A is row-major with float4-loadable rows and B fits the LDS of one
-// of the instances; false = not taken
-bool try_rows(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs,
-              int64_t b_cs, float* C, int64_t M, int64_t N, int64_t K, hipStream_t s) {
-  if (a_cs != 1 || a_rs % 4 != 0 || K % 4 != 0 || !al16(A) || M < 4096) return false;
-  if (N <= 256 && K <= 64) launch_rows<8, 64>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
-  else if (N <= 128 && K <= 128) launch_rows<4, 128>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
-  else if (N <= 64 && K <= 256) launch_rows<2, 256>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
-  else return false;
-  return true;
-}
-
 template <int MB, int NB>
 void launch_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t M,
                int64_t N, int64_t R, int64_t max_blocks, float* partials, hipStream_t s) {
-  int64_t nb = max_blocks < 512 ? max_blocks : 512;
-  int64_t rpb = ((R + nb - 1) / nb + kSlice - 1) / kSlice * kSlice;
-  nb = (R + rpb - 1) / rpb;
+  const int64_t rpb = gemm_tn_rows_per_block(R, max_blocks);
+  const int64_t nb = (R + rpb - 1) / rpb;
   hipLaunchKernelGGL((k_gemm_tn<MB, NB>), dim3(static_cast<unsigned>(nb)), dim3(kGemmThreads), 0, s,
                      A, lda, B, ldb, partials, R, static_cast<int>(M), static_cast<int>(N), rpb);
   hipLaunchKernelGGL(k_sum_splits, dim3(grid1(M * N)), dim3(kBlock), 0, s, partials,
                      static_cast<int>(nb), M * N, C);
-}
-
-// k_gemm_tn for C = A^T B with A (K x M) and B (K x N) row-major (a_rs == 1, b_cs == 1),
-// K the long dimension, through the caller's `splits` partial buffers
-bool try_tn(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs,
-            int64_t b_cs, float* C, int64_t M, int64_t N, int64_t K, int64_t splits,
-            float* partials, hipStream_t s) {
-  if (a_rs != 1 || b_cs != 1 || splits < 2 || partials == nullptr || K < 4096) return false;
-  if (M % 4 != 0 || N % 4 != 0 || a_cs % 4 != 0 || b_rs % 4 != 0 || !al16(A) || !al16(B))
-    return false;
-  if (M <= 64 && N <= 256) launch_tn<2, 8>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
-  else if (M <= 64 && N <= 320) launch_tn<2, 10>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
-  else if (M <= 128 && N <= 128) launch_tn<4, 4>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
-  else if (M <= 256 && N <= 64) launch_tn<8, 2>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
-  else return false;
-  return true;
 }
 
 }  // namespace
@@ -921,10 +941,29 @@ int rgcn_tile_rows() {
   return e != nullptr && std::atoi(e) == 32 ? 32 : 16;
 }
 
+// 32-column blocks of the output held per tile: the width classes <= 32, <= 64, <= 128
+int rgcn_fused_blocks(int64_t out_w) { return out_w <= 32 ? 1 : (out_w <= 64 ? 2 : 4); }
+
 bool rgcn_fused_ok(int64_t gathered_w, int64_t out_w, int64_t R) {
   if (gathered_w != kFusedW || out_w < 1 || out_w > 128 || R < 1) return false;
-  const int64_t nb = out_w <= 32 ? 1 : (out_w <= 64 ? 2 : 4);
-  return R * kFusedW * nb * 32 <= kFusedWsFloats;
+  return R * kFusedW * rgcn_fused_blocks(out_w) * 32 <= kFusedWsFloats;
+}
+
+// The tile height launch_rgcn_fused takes: k_rgcn_fused16 reads the gathered table T
+// (t_rows rows; < 0 = num_rows) by 32-bit byte offsets, so both row counts must stay
+// under 4 GiB of 64-float rows
+int rgcn_fused_tile(int64_t num_rows, int64_t t_rows) {
+  if (t_rows < 0) t_rows = num_rows;
+  return rgcn_tile_rows() == 16 && (num_rows + 1) * kFusedW * 4 < (int64_t(1) << 32) &&
+                 t_rows * kFusedW * 4 < (int64_t(1) << 32)
+             ? 16 : 32;
+}
+
+int rgcn_fused_instance(int64_t gathered_w, int64_t out_w, int64_t R, int64_t num_rows,
+                        int64_t t_rows) {
+  if (!rgcn_fused_ok(gathered_w, out_w, R) || num_rows <= 0) return 0;
+  const int tile = rgcn_fused_tile(num_rows, t_rows);
+  return 100 * tile + rgcn_fused_blocks(out_w) * (tile == 16 ? 2 : 1);
 }
 
 void launch_rgcn_fused(bool bwd, const int32_t* ptr, const int32_t* cols, const int32_t* rows,
@@ -945,10 +984,10 @@ void launch_rgcn_fused(bool bwd, const int32_t* ptr, const int32_t* cols, const 
   if (hipMallocAsync(reinterpret_cast<void**>(&ctr), ctr_bytes, s) != hipSuccess ||
       hipMemsetAsync(ctr, 0, ctr_bytes, s) != hipSuccess)
     throw std::runtime_error("rgcn fused: tile counter allocation failed");
+  const int blocks = rgcn_fused_blocks(out_w);
   // gathered table T: the rows of the relation-major walk's columns (num_rows of them
   // forward, the source rows backward: at most the larger of the two row counts)
-  if (rgcn_tile_rows() == 16 && (num_rows + 1) * kFusedW * 4 < (int64_t(1) << 32) &&
-      t_rows * kFusedW * 4 < (int64_t(1) << 32)) {
+  if (rgcn_fused_tile(num_rows, t_rows) == 16) {
     const int64_t t16 = (num_rows + 15) / 16;
     const int64_t want16 = (t16 + 15) / 16;
     const dim3 grid16(static_cast<unsigned>(want16 < 256 ? want16 : 256)), block16(kR16Threads);
@@ -956,12 +995,12 @@ void launch_rgcn_fused(bool bwd, const int32_t* ptr, const int32_t* cols, const 
   hipLaunchKernelGGL((k_rgcn_fused16<B_, NB_>), grid16, block16, 0, s, ptr, cols, rows, eids, w, T, \
                      W, ws_t, ws_k, ws_n, out, gy, num_rows, Ri, ow, bias, addend, loop_w, ctr)
     if (bwd) {
-      if (out_w <= 32) DGLMI_RGCN_FUSED16(true, 2);
-      else if (out_w <= 64) DGLMI_RGCN_FUSED16(true, 4);
+      if (blocks == 1) DGLMI_RGCN_FUSED16(true, 2);
+      else if (blocks == 2) DGLMI_RGCN_FUSED16(true, 4);
       else DGLMI_RGCN_FUSED16(true, 8);
     } else {
-      if (out_w <= 32) DGLMI_RGCN_FUSED16(false, 2);
-      else if (out_w <= 64) DGLMI_RGCN_FUSED16(false, 4);
+      if (blocks == 1) DGLMI_RGCN_FUSED16(false, 2);
+      else if (blocks == 2) DGLMI_RGCN_FUSED16(false, 4);
       else DGLMI_RGCN_FUSED16(false, 8);
     }
 #undef DGLMI_RGCN_FUSED16
@@ -972,12 +1011,12 @@ void launch_rgcn_fused(bool bwd, const int32_t* ptr, const int32_t* cols, const 
   hipLaunchKernelGGL((k_rgcn_fused<B_, NB_>), grid, block, 0, s, ptr, cols, rows, eids, w, T, W, \
                      ws_t, ws_k, ws_n, out, gy, num_rows, Ri, ow, bias, addend, loop_w, ctr)
   if (bwd) {
-    if (out_w <= 32) DGLMI_RGCN_FUSED(true, 1);
-    else if (out_w <= 64) DGLMI_RGCN_FUSED(true, 2);
+    if (blocks == 1) DGLMI_RGCN_FUSED(true, 1);
+    else if (blocks == 2) DGLMI_RGCN_FUSED(true, 2);
     else DGLMI_RGCN_FUSED(true, 4);
   } else {
-    if (out_w <= 32) DGLMI_RGCN_FUSED(false, 1);
-    else if (out_w <= 64) DGLMI_RGCN_FUSED(false, 2);
+    if (blocks == 1) DGLMI_RGCN_FUSED(false, 1);
+    else if (blocks == 2) DGLMI_RGCN_FUSED(false, 2);
     else DGLMI_RGCN_FUSED(false, 4);
   }
 #undef DGLMI_RGCN_FUSED
@@ -992,9 +1031,19 @@ void launch_gemm(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int
     launch_fill(C, M * N, 0.0f, s);
     return;
   }
-  if (try_rows(A, a_rs, a_cs, B, b_rs, b_cs, C, M, N, K, s)) return;
-  if (try_tn(A, a_rs, a_cs, B, b_rs, b_cs, C, M, N, K, splits, partials, s)) return;
-  const int64_t k_split = ((K + splits - 1) / splits + kTK - 1) / kTK * kTK;
+  // k_gemm_tn reduces through the caller's partial buffers
+  const int64_t tn_splits = partials != nullptr ? splits : 1;
+  switch (gemm_instance(M, N, K, a_rs, a_cs, b_rs, b_cs, al16(A), al16(B), tn_splits)) {
+    case GEMM_ROWS_8_64: return launch_rows<8, 64>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
+    case GEMM_ROWS_4_128: return launch_rows<4, 128>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
+    case GEMM_ROWS_2_256: return launch_rows<2, 256>(A, a_rs, B, b_rs, b_cs, C, M, N, K, s);
+    case GEMM_TN_2_8: return launch_tn<2, 8>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
+    case GEMM_TN_2_10: return launch_tn<2, 10>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
+    case GEMM_TN_4_4: return launch_tn<4, 4>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
+    case GEMM_TN_8_2: return launch_tn<8, 2>(A, a_cs, B, b_rs, C, M, N, K, splits, partials, s);
+    default: break;
+  }
+  const int64_t k_split = gemm_k_split(K, splits);
   const int64_t used = (K + k_split - 1) / k_split;
   const dim3 grid(static_cast<unsigned>(((M + kTM - 1) / kTM) * ((N + kTN - 1) / kTN)), 1,
                   static_cast<unsigned>(used));

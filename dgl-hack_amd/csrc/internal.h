@@ -722,6 +722,21 @@ void launch_add_into(float* out, const float* a, int64_t n, hipStream_t s);
 void launch_gather_f32(const float* v, const int32_t* idx, int64_t n, float* out, hipStream_t s);
 void launch_iota_i32(int32_t* out, int64_t n, hipStream_t s);
 int64_t gemm_splits(int64_t M, int64_t N, int64_t K);
+// The kernel launch_gemm takes (the codes of dglmi.h DGLMIRgcnGemmInstance; `splits`
+// counts only when the caller passes partial buffers), k_gemm's reduction range per
+// split, and k_gemm_tn's rows per block: pure host rules, shared with the C queries.
+enum GemmInstance : int {
+  GEMM_NONE = -1, GEMM_GENERIC = 0, GEMM_ROWS_8_64 = 1, GEMM_ROWS_4_128 = 2, GEMM_ROWS_2_256 = 3,
+  GEMM_TN_2_8 = 4, GEMM_TN_2_10 = 5, GEMM_TN_4_4 = 6, GEMM_TN_8_2 = 7
+};
+int gemm_instance(int64_t M, int64_t N, int64_t K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                  int64_t b_cs, bool a_aligned16, bool b_aligned16, int64_t splits);
+int64_t gemm_k_split(int64_t K, int64_t splits);
+int64_t gemm_tn_rows_per_block(int64_t R, int64_t max_blocks);
+// 0 = not fused (rgcn_fused_ok false or no rows), else 100 * tile height + the
+// instance's column-block template argument (dglmi.h DGLMIRgcnFusedInstance)
+int rgcn_fused_instance(int64_t gathered_w, int64_t out_w, int64_t R, int64_t num_rows,
+                        int64_t t_rows);
 void launch_gemm(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs,
                  int64_t b_cs, float* C, int64_t M, int64_t N, int64_t K, int64_t splits,
                  float* partials, hipStream_t s);

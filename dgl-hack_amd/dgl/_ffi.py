@@ -372,6 +372,10 @@ _SIGS = {
     "DGLMIRgcnRefreshNorm": (ctypes.c_int, [
         ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.POINTER(RgcnState), ctypes.c_void_p]),
     "DGLMIRgcnRelease": (ctypes.c_int, [ctypes.POINTER(RgcnState)]),
+    "DGLMIRgcnGemmSplits": (ctypes.c_int64, [ctypes.c_int64] * 3),
+    "DGLMIRgcnGemmInstance": (ctypes.c_int, [ctypes.c_int64] * 7 + [ctypes.c_int, ctypes.c_int,
+                                                                   ctypes.c_int64]),
+    "DGLMIRgcnFusedInstance": (ctypes.c_int, [ctypes.c_int64] * 5),
     "DGLMINbAccess": (ctypes.c_int, [
         ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),

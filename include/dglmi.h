@@ -697,6 +697,53 @@ int DGLMIRgcnLayer1BackwardEx(const DGLMIGraph* graph, const DGLMIArray* hidden,
                               const DGLMIArray* loop_weight, const DGLMIArray* grad_out,
                               DGLMIArray* grad_hidden, DGLMIArray* grad_weight,
                               DGLMIArray* grad_loop_weight, void* stream);
+/* Which kernels the layer-1 entries launch (extension; for tests and probes).  Pure host
+ * functions: no HIP call, usable without a device.  The launchers call the same rules.
+ * The entries' dense products are C (m x n, row-major) = A (m x k) . B (k x n), A and B
+ * by (row, column) strides in floats:
+ *   forward          hidden (N x F_in) . W_cat (F_in x R F_out): A (F_in, 1), B (R F_out, 1);
+ *   grad_hidden      gy (N x R F_out) . W_cat^T: A (R F_out, 1), B (1, R F_out);
+ *   weight gradient  hidden^T (F_in x N) . gy (N x R F_out): A (1, F_in), B (R F_out, 1),
+ *                    reduction split DGLMIRgcnGemmSplits(F_in, R F_out, N) ways;
+ *   self-loop        hidden . loop (N, F_out, F_in), grad_out . loop^T (N, F_in, F_out; B
+ *                    (1, F_out)) and hidden^T . grad_out (F_in, F_out, N; split as above).
+ * DGLMIRgcnGemmSplits(m, n, k): the reduction splits the entries ask for (a power of two,
+ * 1 .. 2048).
+ * DGLMIRgcnGemmInstance(...): the kernel for one product; a_aligned16 / b_aligned16 say
+ * whether A's and B's base pointers are 16-byte aligned, `splits` is the split count
+ * passed with partial buffers (1 = none):
+ *   -1  no product kernel (m, n or k <= 0)
+ *    0  k_gemm.  It then splits the reduction into ceil(k / ks) ranges, ks = ceil(k /
+ *       splits) rounded up to a multiple of 32 (so fewer than `splits` when k is short)
+ *    1  k_gemm_rows<8,64>    (n <= 256, k <= 64)
+ *    2  k_gemm_rows<4,128>   (n <= 128, k <= 128)
+ *    3  k_gemm_rows<2,256>   (n <= 64,  k <= 256)
+ *         each: m >= 4096, A row-major (a_cs == 1), a_rs % 4 == 0, k % 4 == 0, A aligned
+ *    4  k_gemm_tn<2,8>       (m <= 64,  n <= 256)
+ *    5  k_gemm_tn<2,10>      (m <= 64,  n <= 320)
+ *    6  k_gemm_tn<4,4>       (m <= 128, n <= 128)
+ *    7  k_gemm_tn<8,2>       (m <= 256, n <= 64)
+ *         each: k >= 4096, splits >= 2, a_rs == 1, b_cs == 1, m, n, a_cs, b_rs % 4 == 0,
+ *         A and B aligned; the first matching line wins, k_gemm_rows before k_gemm_tn.
+ * DGLMIRgcnFusedInstance(gathered_w, out_w, rels_incl_loop, num_rows, t_rows): the fused
+ * walk for rows of gathered_w floats (F_in forward, F_out backward), out_w output columns
+ * (F_out forward, F_in backward), rels_incl_loop weight matrices (num_rels, + 1 with a
+ * self-loop weight), num_rows walked rows (destinations forward, sources backward) and
+ * t_rows rows of the gathered table (< 0: num_rows).  0 = not fused (gathered_w != 64,
+ * out_w outside 1 .. 128, the matrices past 20480 LDS floats at out_w rounded up to 32 /
+ * 64 / 128, or no rows); else 100 * tile height + column blocks: 1602 / 1604 / 1608 =
+ * k_rgcn_fused16<., 2 / 4 / 8> (16-row tiles, 16-column blocks), 3201 / 3202 / 3204 =
+ * k_rgcn_fused<., 1 / 2 / 4> (32-row tiles, 32-column blocks; taken with
+ * DGLMI_RGCN_TILE=32, or when num_rows + 1 or t_rows rows of 256 bytes reach 4 GiB).
+ * This is the shape part of the rule only: an entry also needs a prepared state with
+ * layers bit 2 that matches the call, a graph with edges, and a 16-byte aligned gathered
+ * table (hidden forward, grad_out backward); otherwise it takes the products above. */
+int64_t DGLMIRgcnGemmSplits(int64_t m, int64_t n, int64_t k);
+int DGLMIRgcnGemmInstance(int64_t m, int64_t n, int64_t k, int64_t a_rs, int64_t a_cs,
+                          int64_t b_rs, int64_t b_cs, int a_aligned16, int b_aligned16,
+                          int64_t splits);
+int DGLMIRgcnFusedInstance(int64_t gathered_w, int64_t out_w, int64_t rels_incl_loop,
+                           int64_t num_rows, int64_t t_rows);
 /* _CAPI_DGLNbAccess: the in-neighbour gather benchmark.  Runs `times` in-neighbour
  * row gathers of feat over the in-CSR (the load-balanced copy_u sum, into scratch;
  * the reference's timed kernels read rows without using them) and writes the mean
