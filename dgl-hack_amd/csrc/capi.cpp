@@ -3010,6 +3010,65 @@ int DGLMICsrGatherRows(const DGLMICsr* csr, int32_t num_bits, const int32_t* row
   API_END();
 }
 
+int DGLMISampleNeighborsWeighted(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds,
+                                 int64_t num_seeds, int32_t fanout, int32_t replace,
+                                 const void* weight, int64_t num_weights, int32_t weight_dtype,
+                                 uint64_t rng_seed, uint64_t rng_ctr, int64_t* offsets,
+                                 int64_t num_out, int32_t* out_nbr, int64_t* out_eid, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(fanout >= 0 && fanout <= sample_max_fanout(),
+              "weighted sample: fanout must be between 0 and " +
+                  std::to_string(sample_max_fanout()) + ", got " + std::to_string(fanout));
+  DGLMI_CHECK(weight_dtype == DGLMI_WEIGHT_F32 || weight_dtype == DGLMI_WEIGHT_F64,
+              "weighted sample: the weights must be float32 or float64");
+  const SampleCsr c = sample_csr(csr, num_bits);
+  DGLMI_CHECK(num_seeds >= 0 && num_seeds < (int64_t(1) << 31), "weighted sample: bad seed count");
+  DGLMI_CHECK(num_seeds == 0 || seeds != nullptr, "null seeds");
+  DGLMI_CHECK(num_weights >= 0 && (num_weights == 0 || weight != nullptr), "null weight");
+  DGLMI_CHECK(offsets != nullptr, "null offsets");
+  DGLMI_CHECK(num_out >= 0, "negative num_out");
+  DeviceGuard guard(device_of(offsets, "weighted sample offsets: not a device pointer"));
+  if (out_nbr == nullptr) {
+    launch_weighted_count(c, seeds, num_seeds, fanout, replace != 0, weight, num_weights,
+                          weight_dtype, offsets, static_cast<hipStream_t>(stream));
+  } else {
+    DGLMI_CHECK(out_eid != nullptr, "null out_eid");
+    launch_weighted_pick(c, seeds, num_seeds, fanout, replace != 0, weight, num_weights,
+                         weight_dtype, rng_seed, rng_ctr, offsets, num_out, out_nbr, out_eid,
+                         static_cast<hipStream_t>(stream));
+  }
+  check_hip(hipGetLastError(), "weighted sample launch");
+  API_END();
+}
+
+int DGLMISelectTopk(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds, int64_t num_seeds,
+                    int32_t k, int32_t ascending, const void* weight, int64_t num_weights,
+                    int32_t weight_dtype, int64_t* offsets, int64_t num_out, int32_t* out_nbr,
+                    int64_t* out_eid, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(k >= 0 && k <= sample_max_fanout(),
+              "select_topk: k must be between 0 and " + std::to_string(sample_max_fanout()) +
+                  ", got " + std::to_string(k));
+  DGLMI_CHECK(weight_dtype >= DGLMI_WEIGHT_F32 && weight_dtype <= DGLMI_WEIGHT_I64,
+              "select_topk: the weights must be float32, float64, int32 or int64");
+  const SampleCsr c = sample_csr(csr, num_bits);
+  DGLMI_CHECK(num_seeds >= 0 && num_seeds < (int64_t(1) << 31), "select_topk: bad seed count");
+  DGLMI_CHECK(num_seeds == 0 || seeds != nullptr, "null seeds");
+  DGLMI_CHECK(num_weights >= 0 && (num_weights == 0 || weight != nullptr), "null weight");
+  DGLMI_CHECK(offsets != nullptr, "null offsets");
+  DGLMI_CHECK(num_out >= 0, "negative num_out");
+  DeviceGuard guard(device_of(offsets, "select_topk offsets: not a device pointer"));
+  if (out_nbr == nullptr) {
+    launch_sample_count(c, seeds, num_seeds, k, 0, offsets, static_cast<hipStream_t>(stream));
+  } else {
+    DGLMI_CHECK(out_eid != nullptr, "null out_eid");
+    launch_select_topk(c, seeds, num_seeds, k, ascending != 0, weight, num_weights, weight_dtype,
+                       offsets, num_out, out_nbr, out_eid, static_cast<hipStream_t>(stream));
+  }
+  check_hip(hipGetLastError(), "select_topk launch");
+  API_END();
+}
+
 int DGLMIBlockRelabelMark(int32_t* table, int64_t num_nodes, const int32_t* dst_nodes, int64_t S,
                           const int32_t* src, int64_t E, int32_t include_dst, int32_t* flags,
                           void* stream) {

@@ -819,6 +819,20 @@ void launch_relabel_write(int32_t* table, int64_t num_nodes, const int32_t* dst_
                           const int32_t* scan, int64_t* src_nodes, int32_t* new_src, int64_t* counts,
                           hipStream_t s);
 
+// weighted sampling and row-wise top-k (kernels_sample_weighted.hip): see
+// DGLMISampleNeighborsWeighted and DGLMISelectTopk.  `code` is a DGLMIWeightDtype.
+void launch_weighted_count(const SampleCsr& c, const int32_t* seeds, int64_t num_seeds, int fanout,
+                           int replace, const void* weight, int64_t num_weights, int code,
+                           int64_t* cnt, hipStream_t s);
+void launch_weighted_pick(const SampleCsr& c, const int32_t* seeds, int64_t num_seeds, int fanout,
+                          int replace, const void* weight, int64_t num_weights, int code,
+                          uint64_t rng_seed, uint64_t rng_ctr, const int64_t* offsets,
+                          int64_t num_out, int32_t* out_nbr, int64_t* out_eid, hipStream_t s);
+void launch_select_topk(const SampleCsr& c, const int32_t* seeds, int64_t num_seeds, int k,
+                        int ascending, const void* weight, int64_t num_weights, int code,
+                        const int64_t* offsets, int64_t num_out, int32_t* out_nbr, int64_t* out_eid,
+                        hipStream_t s);
+
 // random walks and visit counts (kernels_walk.hip): see DGLMIRandomWalk and DGLMIVisitTopK.
 // The relations' out-CSRs travel by value in the kernel argument: no device allocation.
 constexpr int kWalkMaxRels = 16;

@@ -417,6 +417,15 @@ _SIGS = {
     "DGLMICsrGatherRows": (ctypes.c_int, [
         ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMISampleNeighborsWeighted": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64,
+        ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    "DGLMISelectTopk": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "DGLMIBlockRelabelMark": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),

@@ -1306,6 +1306,40 @@ def sample_neighbors(csr, seeds, fanout, replace, rng_seed, rng_ctr=0):
     return _two_phase(L.DGLMISampleNeighbors, csr, seeds, head, ())
 
 
+_WEIGHT_CODES = {th.float32: 0, th.float64: 1, th.int32: 2, th.int64: 3}  # DGLMIWeightDtype
+
+
+def _weight_head(weight, dev, allowed, what):
+    if (not isinstance(weight, th.Tensor) or weight.dim() != 1 or weight.device != dev
+            or weight.dtype not in allowed):
+        raise DGLError("%s: weight must be a 1-D tensor on %s of dtype %s"
+                       % (what, dev, " or ".join(str(d) for d in allowed)))
+    weight = weight.contiguous()
+    return weight, (_vp(weight), int(weight.shape[0]), _WEIGHT_CODES[weight.dtype])
+
+
+def sample_neighbors_weighted(csr, seeds, fanout, replace, weight, rng_seed, rng_ctr=0):
+    """Up to ``fanout`` entries of every row ``seeds[i]`` of ``csr``, drawn in proportion to
+    ``weight`` (float32 or float64 on the device, indexed by parent edge id) ->
+    DGLMISampleNeighborsWeighted, whose header states eligibility, the counts, the draws and
+    the order.  Returns (offsets, nbr, eid) like ``sample_neighbors``."""
+    weight, wh = _weight_head(weight, csr.indptr.device, (th.float32, th.float64),
+                              "sample_neighbors_weighted")
+    head = (int(fanout), 1 if replace else 0) + wh + (int(rng_seed) & (2 ** 64 - 1),
+                                                      int(rng_ctr) & (2 ** 64 - 1))
+    return _two_phase(_ffi.lib().DGLMISampleNeighborsWeighted, csr, seeds, head, ())
+
+
+def select_topk(csr, seeds, k, weight, ascending=False):
+    """The ``k`` entries of every row ``seeds[i]`` of ``csr`` with the largest (smallest when
+    ``ascending``) ``weight`` (float32, float64, int32 or int64 on the device, indexed by
+    parent edge id), listed in that order -> DGLMISelectTopk.  Returns (offsets, nbr, eid)
+    like ``sample_neighbors``."""
+    weight, wh = _weight_head(weight, csr.indptr.device, tuple(_WEIGHT_CODES), "select_topk")
+    head = (int(k), 1 if ascending else 0) + wh
+    return _two_phase(_ffi.lib().DGLMISelectTopk, csr, seeds, head, ())
+
+
 def csr_gather_rows(csr, rows):
     """Every entry of the rows ``rows[i]`` of ``csr``, row by row in CSR order ->
     DGLMICsrGatherRows.  Returns (offsets, nbr, eid) like ``sample_neighbors``."""

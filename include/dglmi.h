@@ -961,6 +961,87 @@ int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst
                            const int32_t* scan, int64_t* src_nodes, int32_t* new_src,
                            int64_t* counts, void* stream);
 
+/* ---- weighted neighbour sampling and row-wise top-k ------------------------------
+ * dgl.sampling.sample_neighbors(prob=...) and dgl.sampling.select_topk
+ * (sampling/neighbor.py:11-167, rowwise_sampling.cc, rowwise_topk.cc).  Both entries take
+ * the common arguments of DGLMISampleNeighbors and its two-phase protocol (out_nbr == NULL
+ * is the count phase), and list a seed's picks at offsets[i] .. offsets[i + 1] - 1.
+ *
+ * weight: a device array of num_weights values of the type weight_dtype names, indexed by
+ *   PARENT EDGE ID: the weight of the entry at position p of a row that starts at `start` is
+ *   weight[data[start + p]].  An edge id outside [0, num_weights) has no weight: it is never
+ *   drawn by the sampler and ranks with the NaNs in the top-k.
+ *
+ * The picks are a function of the arguments alone and have the same bits on every run: no
+ *   atomics, nothing whose value depends on a reduction order, no libm call.
+ *
+ * DGLMISampleNeighborsWeighted.  weight_dtype: DGLMI_WEIGHT_F32 or DGLMI_WEIGHT_F64.
+ *   An entry is ELIGIBLE when its weight is finite and greater than 0 and, for fp64, at
+ *   least 2^-900 (so that the key below cannot overflow).  Every other entry -- NaN, +-inf,
+ *   negative, zero, fp64 below 2^-900 -- has weight 0 and is never drawn.  With nz the
+ *   number of eligible entries of the row of seeds[i]:
+ *     cnt[i] = 0                when nz = 0,
+ *     cnt[i] = fanout           when nz > 0 and replace != 0,
+ *     cnt[i] = min(nz, fanout)  when nz > 0 and replace == 0.
+ *   This deviates from the reference on purpose: the reference returns a whole row, edges
+ *   of probability zero included, when deg <= fanout, and its behaviour is undefined when
+ *   nz < fanout < deg.  Here no ineligible edge is ever returned.
+ *   0 <= fanout <= DGLMISampleMaxFanout().  The picks are listed in ascending CSR position;
+ *   repeats under replacement are adjacent.
+ *
+ *   replace == 0 (the reference's draw-and-remove TreeSampler, realised as exponential
+ *   keys: the same distribution in one pass over the row).  When nz <= fanout every
+ *   eligible entry is taken.  Otherwise the entry at position p (a 64-bit value) of seed
+ *   slot i takes the draw r = r(i, p) of DGLMISampleNeighbors: component p & 3 of the block
+ *   at counter rng_ctr + (p >> 2).  E(r) is the integer -log2((r + 1/2) / 2^32) in 40
+ *   fractional bits, computed so:
+ *     y = 2 r + 1;  n = floor(log2 y);  m = y << (63 - n);  bits = 0;
+ *     forty times:  sq = (m m) >> 63 (a value below 2^65);
+ *                   sq >= 2^64:  bits = 2 bits + 1, m = sq >> 1;
+ *                   otherwise:   bits = 2 bits,     m = sq;
+ *     E = (33 << 40) - ((n << 40) + bits).
+ *   |E / 2^40 - exact| <= 9.1e-13 (measured over the extreme and 2,000 random draws) and
+ *   185 <= E < 2^46.  The entry's key is the fp64 quotient double(E) / double(w): both
+ *   conversions are exact and the IEEE division is correctly rounded, so the key has one
+ *   value everywhere.  The picks are the fanout eligible entries smallest in (the key's bits
+ *   as uint64, position).
+ *
+ *   replace != 0.  With e the binary exponent of the row's largest eligible weight
+ *   (max = f 2^e, 1/2 <= f < 1), q_p = floor(w_p 2^(31 - e)) for an eligible entry and 0 for
+ *   any other: an exact power-of-two scaling and a floor, q_p < 2^31.  total = sum of q_p,
+ *   an integer below 2^63 for any degree below 2^32, the same in any order of summation.
+ *   Draw t = 0 .. fanout - 1 takes R_t = hi 2^32 + lo, (lo, hi) the words (x, y) for even t
+ *   and (z, w) for odd t of the Philox block at counter rng_ctr + (t >> 1) mod 2^64 of slot
+ *   i (the counter and key layout of DGLMISampleNeighbors).  T = floor(R_t total / 2^64);
+ *   the pick is the lowest position whose inclusive running sum of q exceeds T.  Then
+ *   sorted.  Consequences: an entry below 2^-31 of its row's largest weight has q = 0 and is
+ *   never drawn under replacement (it is drawn without); an entry's probability
+ *   q_p / total differs from w_p / sum(w) by at most 1 / q_p in relative terms from the
+ *   floor, plus total / 2^64 from the scaling of R_t.
+ *
+ * DGLMISelectTopk.  weight_dtype: any of the four (the reference's).  cnt[i] = min(deg, k),
+ *   0 <= k <= DGLMISampleMaxFanout().  The picks are the cnt entries first in the strict
+ *   total order (weight, descending unless `ascending` != 0; then ascending position), and
+ *   are listed in that order: the reference's output order with its unspecified tie rule
+ *   pinned.  -0.0 counts as +0.0; a NaN ranks after every number in both directions.
+ *   Unlike the reference, a row with deg <= k is listed in weight order too, not CSR
+ *   order. */
+enum DGLMIWeightDtype {
+  DGLMI_WEIGHT_F32 = 0,
+  DGLMI_WEIGHT_F64 = 1,
+  DGLMI_WEIGHT_I32 = 2,
+  DGLMI_WEIGHT_I64 = 3
+};
+int DGLMISampleNeighborsWeighted(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds,
+                                 int64_t num_seeds, int32_t fanout, int32_t replace,
+                                 const void* weight, int64_t num_weights, int32_t weight_dtype,
+                                 uint64_t rng_seed, uint64_t rng_ctr, int64_t* offsets,
+                                 int64_t num_out, int32_t* out_nbr, int64_t* out_eid, void* stream);
+int DGLMISelectTopk(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds, int64_t num_seeds,
+                    int32_t k, int32_t ascending, const void* weight, int64_t num_weights,
+                    int32_t weight_dtype, int64_t* offsets, int64_t num_out, int32_t* out_nbr,
+                    int64_t* out_eid, void* stream);
+
 /* ---- random walks and visit counts ------------------------------------------
  * dgl.sampling.random_walk and the counting step of RandomWalkNeighborSampler /
  * PinSAGESampler (_CAPI_DGLSamplingRandomWalk, ..WithRestart, ..WithStepwiseRestart;
