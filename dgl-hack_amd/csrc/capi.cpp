@@ -2386,15 +2386,13 @@ int rgcn_layer1_backward_impl(const DGLMIGraph* graph,
     if (!loop) {
       launch_permute_rkx(static_cast<float*>(gw.ptr), R, K, X, false, grad_weight->data, s);
     } else {
-      // gw (K x (R + 1) X) -> [R + 1][K][X]: the relation blocks, then the self-loop one
-      Scratch gp(no_workspace(), (R + 1) * K * X * 4, s);
-      float* p = static_cast<float*>(gp.ptr);
-      launch_permute_rkx(static_cast<float*>(gw.ptr), R + 1, K, X, false, p, s);
-      check_hip(hipMemcpyAsync(grad_weight->data, p, R * K * X * 4, hipMemcpyDeviceToDevice, s),
-                "copy grad_weight");
-      if (grad_loop)
-        check_hip(hipMemcpyAsync(grad_loop->data, p + R * K * X, K * X * 4,
-                                 hipMemcpyDeviceToDevice, s), "copy grad_loop_weight");
+      // gw (K x (R + 1) X): the relation blocks to grad_weight [R][K][X], the self-loop
+      // one to grad_loop, each by a kernel and not a device-to-device copy of a permuted
+      // scratch: recorded into a captured graph, such a copy gave the first replay the
+      // scratch's bytes from before the permute in the first block
+      const float* p = static_cast<const float*>(gw.ptr);
+      launch_unpack_rkx(p, MG, R, K, X, grad_weight->data, s);
+      if (grad_loop) launch_unpack_rkx(p + R * X, MG, 1, K, X, grad_loop->data, s);
     }
     check_hip(hipGetLastError(), "rgcn fused layer1 backward launch");
     return 0;

@@ -33,14 +33,15 @@ __global__ void k_typed_ids(const int32_t* __restrict__ ids, const int32_t* __re
   }
 }
 
-// to_cat: out[k, r*X + x] = w[r, k, x]; else out[r, k, x] = w[k, r*X + x]
+// to_cat: out[k, r*X + x] = w[r, k, x]; else out[r, k, x] = w[k, r*X + x]; the
+// (k, r*X + x) side has rows of `ld` floats (R * X, or more: a slice of wider rows)
 __global__ void k_permute_rkx(const float* __restrict__ w, int64_t R, int64_t K, int64_t X,
-                              bool to_cat, float* __restrict__ out) {
+                              int64_t ld, bool to_cat, float* __restrict__ out) {
   const int64_t n = R * K * X;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t x = i % X, k = (i / X) % K, r = i / (X * K);  // i = (r, k, x)
-    const int64_t j = k * R * X + r * X + x;                      // (k, r*X + x)
+    const int64_t j = k * ld + r * X + x;                         // (k, r*X + x)
     if (to_cat) out[j] = w[i];
     else out[i] = w[j];
   }
@@ -846,8 +847,15 @@ void launch_add_into(float* out, const float* a, int64_t n, hipStream_t s) {
 void launch_permute_rkx(const float* w, int64_t R, int64_t K, int64_t X, bool to_cat, float* out,
                         hipStream_t s) {
   if (R * K * X <= 0) return;
-  hipLaunchKernelGGL(k_permute_rkx, dim3(grid1(R * K * X)), dim3(kBlock), 0, s, w, R, K, X, to_cat,
-                     out);
+  hipLaunchKernelGGL(k_permute_rkx, dim3(grid1(R * K * X)), dim3(kBlock), 0, s, w, R, K, X, R * X,
+                     to_cat, out);
+}
+
+void launch_unpack_rkx(const float* cat, int64_t ld, int64_t R, int64_t K, int64_t X, float* out,
+                       hipStream_t s) {
+  if (R * K * X <= 0) return;
+  hipLaunchKernelGGL(k_permute_rkx, dim3(grid1(R * K * X)), dim3(kBlock), 0, s, cat, R, K, X, ld,
+                     false, out);
 }
 
 int64_t gemm_splits(int64_t M, int64_t N, int64_t K) {
@@ -978,12 +986,13 @@ void launch_rgcn_fused(bool bwd, const int32_t* ptr, const int32_t* cols, const 
   const int64_t want = (tiles + 7) / 8;
   const dim3 grid(static_cast<unsigned>(want < 256 ? want : 256)), block(kGemmThreads);
   const int Ri = static_cast<int>(R), ow = static_cast<int>(out_w);
-  // the tile queue's counter: stream-ordered, zeroed before and released after
+  // the tile queue's counter: stream-ordered, zeroed before and released after (by a
+  // kernel: a captured step then holds kernel nodes only, no memset node)
   unsigned* ctr = nullptr;
   const size_t ctr_bytes = 8 * kCtrStride * sizeof(unsigned);
-  if (hipMallocAsync(reinterpret_cast<void**>(&ctr), ctr_bytes, s) != hipSuccess ||
-      hipMemsetAsync(ctr, 0, ctr_bytes, s) != hipSuccess)
+  if (hipMallocAsync(reinterpret_cast<void**>(&ctr), ctr_bytes, s) != hipSuccess)
     throw std::runtime_error("rgcn fused: tile counter allocation failed");
+  launch_fill_i32(reinterpret_cast<int32_t*>(ctr), 8 * kCtrStride, 0, s);
   const int blocks = rgcn_fused_blocks(out_w);
   // gathered table T: the rows of the relation-major walk's columns (num_rows of them
   // forward, the source rows backward: at most the larger of the two row counts)

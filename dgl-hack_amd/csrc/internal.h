@@ -703,6 +703,9 @@ void launch_typed_ids(const int32_t* ids, const int32_t* eids, const int32_t* et
                       int64_t mul, int mode, int32_t* out, hipStream_t s);
 void launch_permute_rkx(const float* w, int64_t R, int64_t K, int64_t X, bool to_cat, float* out,
                         hipStream_t s);
+// out[r, k, x] = cat[k * ld + r * X + x]: R blocks out of rows of ld >= R * X floats
+void launch_unpack_rkx(const float* cat, int64_t ld, int64_t R, int64_t K, int64_t X, float* out,
+                       hipStream_t s);
 // Fused R-GCN layer 1 (hack_kernels.hip k_rgcn_fused): the relation-major CSR (rows
 // t * num_rows + v, `rows` = its COO rows, eids NULL = w by position), gathered table T
 // of 64-float rows, weights W[t][k][n] by strides; out (num_rows x out_w); bwd also
