@@ -12,7 +12,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -143,12 +145,25 @@ size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // ---- 64-bit graphs (2^31 or more edges): int64 offsets and edge ids ----------
 // COO -> CSR as a stable counting sort by row done in batches of at most 2^30
-// positions, in position order.  Row counts (atomics) and their exclusive scan give
-// indptr; each batch is sorted by (row, position) with the same stable radix sort
-// as the int32 path (int item counts), and its run of row r is written after the
-// runs of the earlier batches (a per-row fill cursor), so every row keeps its
-// positions ascending: bit-identical to COOToCSR with int64 arrays.
+// positions (ingest_batch64), in position order.  Row counts (atomics) and their
+// exclusive scan give indptr; each batch is sorted by (row, position) with the same
+// stable radix sort as the int32 path (int item counts), and its run of row r is
+// written after the runs of the earlier batches (a per-row fill cursor), so every row
+// keeps its positions ascending: bit-identical to COOToCSR with int64 arrays.
 constexpr int64_t kBatch64 = int64_t(1) << 30;
+
+// The batch length of a call: kBatch64, or DGLMI_INGEST_BATCH when it parses to an
+// integer in [1, 2^30] (anything else is ignored).  Read per call: tests move the batch
+// seams with it.  The workspace layout and both batch loops take their length from here.
+int64_t ingest_batch64() {
+  const char* e = std::getenv("DGLMI_INGEST_BATCH");
+  if (e == nullptr || *e == '\0') return kBatch64;
+  char* end = nullptr;
+  errno = 0;
+  const long long v = std::strtoll(e, &end, 10);
+  if (errno != 0 || *end != '\0' || v < 1 || v > kBatch64) return kBatch64;
+  return static_cast<int64_t>(v);
+}
 
 __global__ void k_count_rows64(const int32_t* __restrict__ row, int64_t nnz,
                                unsigned long long* __restrict__ cnt) {
@@ -204,8 +219,8 @@ struct Ws64 {
   size_t fill, keys, perm_in, perm_out, rs, temp, total;
 };
 
-Ws64 ws64_layout(int64_t n, int64_t nnz) {
-  const int64_t b = nnz < kBatch64 ? nnz : kBatch64;
+Ws64 ws64_layout(int64_t n, int64_t nnz, int64_t batch) {
+  const int64_t b = nnz < batch ? nnz : batch;
   size_t sort_b = 0, scan_b = 0, max_b = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, static_cast<const int32_t*>(nullptr),
                                            static_cast<int32_t*>(nullptr),
@@ -329,7 +344,7 @@ int DGLMICOOToCSRDevice(int64_t num_rows, int64_t nnz, const int32_t* row, const
 
 int64_t DGLMICOOToCSRDevice64WorkspaceBytes(int64_t num_rows, int64_t nnz) {
   if (nnz <= 0 || num_rows < 0) return 256;
-  return static_cast<int64_t>(ws64_layout(num_rows, nnz).total);
+  return static_cast<int64_t>(ws64_layout(num_rows, nnz, ingest_batch64()).total);
 }
 
 int DGLMICOOToCSRDevice64(int64_t num_rows, int64_t nnz, const int32_t* row, const int32_t* col,
@@ -341,7 +356,8 @@ int DGLMICOOToCSRDevice64(int64_t num_rows, int64_t nnz, const int32_t* row, con
     if (hipMemsetAsync(indptr, 0, (num_rows + 1) * sizeof(int64_t), s) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  const Ws64 w = ws64_layout(num_rows, nnz);
+  const int64_t batch = ingest_batch64();
+  const Ws64 w = ws64_layout(num_rows, nnz, batch);
   if (workspace == nullptr || workspace_bytes < static_cast<int64_t>(w.total)) return -1;
   char* ws = static_cast<char*>(workspace);
   int64_t* fill = reinterpret_cast<int64_t*>(ws + w.fill);
@@ -362,8 +378,8 @@ int DGLMICOOToCSRDevice64(int64_t num_rows, int64_t nnz, const int32_t* row, con
   if (hipMemcpyAsync(fill, indptr, num_rows * sizeof(int64_t), hipMemcpyDeviceToDevice, s) !=
       hipSuccess)
     return -1;
-  for (int64_t start = 0; start < nnz; start += kBatch64) {
-    const int64_t nb = std::min(kBatch64, nnz - start);
+  for (int64_t start = 0; start < nnz; start += batch) {
+    const int64_t nb = std::min(batch, nnz - start);
     hipLaunchKernelGGL(k_iota, dim3(grid_of(nb)), dim3(256), 0, s, perm_in, nb);
     tb = temp_cap;
     if (hipcub::DeviceRadixSort::SortPairs(temp, tb, row + start, keys, perm_in, perm_out,
@@ -390,15 +406,16 @@ int DGLMICSRExpandRows64(const int64_t* indptr, int64_t num_rows, int64_t nnz, i
   dglmi::launch_fill_i32(rows, nnz, 0, s);
   hipLaunchKernelGGL(k_mark_row_starts64, dim3(grid_of(num_rows)), dim3(256), 0, s, indptr, num_rows,
                      rows);
-  const int64_t b = std::min(kBatch64, nnz);
+  const int64_t batch = ingest_batch64();
+  const int64_t b = std::min(batch, nnz);
   size_t temp_bytes = 0;
   (void)hipcub::DeviceScan::InclusiveScan(nullptr, temp_bytes, rows, rows, MaxOp(), static_cast<int>(b),
                                           s);
   void* temp = nullptr;
   if (hipMallocAsync(&temp, temp_bytes, s) != hipSuccess) return -1;
   hipError_t e = hipSuccess;
-  for (int64_t start = 0; start < nnz && e == hipSuccess; start += kBatch64) {
-    const int64_t nb = std::min(kBatch64, nnz - start);
+  for (int64_t start = 0; start < nnz && e == hipSuccess; start += batch) {
+    const int64_t nb = std::min(batch, nnz - start);
     if (start > 0) hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(64), 0, s, rows, start);
     size_t tb = temp_bytes;
     e = hipcub::DeviceScan::InclusiveScan(temp, tb, rows + start, rows + start, MaxOp(),

@@ -307,7 +307,11 @@ int DGLMICSRExpandRows(const int32_t* indptr, int64_t num_rows, int64_t nnz, int
 /* 64-bit graphs (num_bits == 64): device COO -> CSR with int64 offsets and edge ids
  * (row / col int32 node ids, optional int64 data; indptr int64, indices int32,
  * out_data int64), bit-identical to DGLMICOOToCSR; a stable counting sort in
- * batches of 2^30 positions.  Workspace: DGLMICOOToCSRDevice64WorkspaceBytes. */
+ * batches of 2^30 positions.  Workspace: DGLMICOOToCSRDevice64WorkspaceBytes.
+ * DGLMI_INGEST_BATCH=<integer in [1, 2^30]> sets another batch length for these two
+ * entries and DGLMICSRExpandRows64 (read on every call; any other value is ignored):
+ * the arrays do not depend on it, the workspace size does, so size and build under the
+ * same setting. */
 int64_t DGLMICOOToCSRDevice64WorkspaceBytes(int64_t num_rows, int64_t nnz);
 int DGLMICOOToCSRDevice64(int64_t num_rows, int64_t nnz, const int32_t* row, const int32_t* col,
                           const int64_t* data, int64_t* indptr, int32_t* indices,

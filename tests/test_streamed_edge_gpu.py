@@ -288,3 +288,79 @@ def test_gather_rows_matches_indexing(shape, idt):
     for bad in (shape[0], -1):
         with pytest.raises(DGLError, match="out of range"):
             K.gather_rows(src, th.tensor([0, bad], device=DEV, dtype=idt), check=True)
+
+
+def _gather_into_nan(src, idx):
+    """DGLMIGatherRows into a NaN-filled buffer: a store the kernel skips stays NaN,
+    whatever the allocator's block held before (gather_rows' own output is new_empty)."""
+    import ctypes
+    from dgl import _ffi
+    out = th.full((idx.shape[0],) + tuple(src.shape[1:]), float("nan"), device=DEV)
+    row = 1
+    for d in src.shape[1:]:
+        row *= d
+    rc = _ffi.lib().DGLMIGatherRows(
+        ctypes.c_void_p(src.data_ptr()), row, ctypes.c_void_p(idx.data_ptr()),
+        32 if idx.dtype == th.int32 else 64, idx.shape[0], ctypes.c_void_p(out.data_ptr()),
+        ctypes.c_void_p(th.cuda.current_stream(DEV).cuda_stream))
+    assert rc == 0
+    return out
+
+
+# every float4 width 4 << k of k_gather_rows_v4 (k = 0 .. 6) and scalar widths beside them
+GATHER_WIDTHS = [4 << k for k in range(7)] + [1, 5, 12, 512]
+# lanes take two float4 a stride apart: n << SH odd and even, one lane, a full block, one
+# more, and the count of the test above -- the last lane's second store exists or not
+GATHER_COUNTS = [1, 2, 3, 255, 256, 257, 4321]
+
+
+@pytest.mark.parametrize("width", GATHER_WIDTHS)
+@pytest.mark.parametrize("idt", [th.int32, th.int64])
+def test_gather_rows_widths_and_counts(width, idt):
+    """DGLMIGatherRows == src[index] at every float4 width and at scalar widths, for index
+    counts that put the end of the work on the first and on the second float4 of a lane."""
+    rows = 777
+    src = th.randn(rows, width, device=DEV)
+    assert src.data_ptr() % 16 == 0
+    for n in GATHER_COUNTS:
+        idx = th.randint(0, rows, (n,), device=DEV, dtype=idt)
+        idx[-1] = rows - 1  # the last row of the source is read
+        want = src[idx.long()]
+        got = _gather_into_nan(src, idx)
+        assert th.equal(got, want), (width, n)
+        assert th.equal(K.gather_rows(src, idx), want), (width, n)
+
+
+@pytest.mark.parametrize("width", [4, 8, 64, 256])
+def test_gather_rows_unaligned_source(width):
+    """A contiguous source that starts 4 bytes past a 16-byte boundary cannot be read as
+    float4: the scalar kernel takes it, with the same result."""
+    rows = 300
+    flat = th.randn(rows * width + 1, device=DEV)
+    src = flat[1:].view(rows, width)
+    assert src.is_contiguous() and src.data_ptr() % 16 == 4
+    assert src.contiguous().data_ptr() == src.data_ptr()
+    for n in (1, 257, 4321):
+        idx = th.randint(0, rows, (n,), device=DEV, dtype=th.int32)
+        want = flat[1:].reshape(rows, width)[idx.long()]
+        assert th.equal(_gather_into_nan(src, idx), want)
+        assert th.equal(K.gather_rows(src, idx), want)
+
+
+# DGLMIGatherRows launches at most 65536 blocks of 256 lanes.  The scalar kernel takes one
+# row per lane: 65536 * 256 rows fill the grid.  At width 256 a row is 64 float4 and a lane
+# takes two: 65536 * 256 * 2 / 64 = 524288 rows fill it.
+GATHER_GRID_LANES = 65536 * 256
+
+
+@pytest.mark.parametrize("width,n", [(1, GATHER_GRID_LANES + 5),
+                                     (256, GATHER_GRID_LANES * 2 // 64 + 1000)])
+def test_gather_rows_past_the_grid_cap(width, n):
+    """More work than the capped grid covers in one turn: the grid-stride loops go round
+    again (the float4 kernel by two strides at a time)."""
+    assert n in (65536 * 256 + 5, 524288 + 1000)
+    rows = 1000
+    src = th.randn(rows, width, device=DEV)
+    idx = th.randint(0, rows, (n,), device=DEV, dtype=th.int32)
+    want = src[idx.long()]
+    assert th.equal(_gather_into_nan(src, idx), want)
