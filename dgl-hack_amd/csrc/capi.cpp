@@ -3104,6 +3104,57 @@ int DGLMIBlockRelabelWrite(int32_t* table, int64_t num_nodes, const int32_t* dst
   API_END();
 }
 
+// ---- ordered CSR row-and-column slice (kernels_subgraph.hip) ---------------------------
+int32_t DGLMISubgraphTile(void) { return subgraph_tile(); }
+
+namespace {
+
+SampleCsr slice_csr(const DGLMICsr* csr, int32_t num_bits, const int32_t* nodes, int64_t S,
+                    const int64_t* goff, const int32_t* table, int64_t table_len, int64_t max_pos,
+                    const void* keep, const void* tiles) {
+  const SampleCsr c = sample_csr(csr, num_bits);
+  DGLMI_CHECK(S >= 0 && S < (int64_t(1) << 31), "csr slice: bad node count");
+  DGLMI_CHECK(S == 0 || nodes != nullptr, "null nodes");
+  DGLMI_CHECK(goff != nullptr, "null goff");
+  DGLMI_CHECK(table_len >= 0 && (table_len == 0 || table != nullptr), "null table");
+  DGLMI_CHECK(max_pos >= 0 && subgraph_tiles(max_pos) < (int64_t(1) << 31),
+              "csr slice: max_pos must be in [0, 2^31 tiles)");
+  DGLMI_CHECK(max_pos == 0 || (keep != nullptr && tiles != nullptr), "null keep or tile array");
+  return c;
+}
+
+}  // namespace
+
+int DGLMICsrSliceCount(const DGLMICsr* csr, int32_t num_bits, const int32_t* nodes, int64_t num_sel,
+                       const int64_t* goff, const int32_t* table, int64_t table_len,
+                       int64_t max_pos, uint64_t* keep, int64_t* tile_cnt, void* stream) {
+  API_BEGIN();
+  const SampleCsr c =
+      slice_csr(csr, num_bits, nodes, num_sel, goff, table, table_len, max_pos, keep, tile_cnt);
+  DeviceGuard guard(device_of(goff, "csr slice goff: not a device pointer"));
+  launch_slice_count(c, nodes, num_sel, goff, table, table_len, max_pos, keep, tile_cnt,
+                     static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "csr slice count launch");
+  API_END();
+}
+
+int DGLMICsrSliceFill(const DGLMICsr* csr, int32_t num_bits, const int32_t* nodes, int64_t num_sel,
+                      const int64_t* goff, const int32_t* table, int64_t table_len, int64_t max_pos,
+                      const uint64_t* keep, const int64_t* tile_scan, int64_t num_out,
+                      int32_t* new_src, int32_t* new_dst, int64_t* parent_eid, void* stream) {
+  API_BEGIN();
+  const SampleCsr c =
+      slice_csr(csr, num_bits, nodes, num_sel, goff, table, table_len, max_pos, keep, tile_scan);
+  DGLMI_CHECK(num_out >= 0, "negative num_out");
+  DGLMI_CHECK(num_out == 0 || (new_src != nullptr && new_dst != nullptr && parent_eid != nullptr),
+              "null output");
+  DeviceGuard guard(device_of(goff, "csr slice goff: not a device pointer"));
+  launch_slice_fill(c, nodes, num_sel, goff, table, table_len, max_pos, keep, tile_scan, num_out,
+                    new_src, new_dst, parent_eid, static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "csr slice fill launch");
+  API_END();
+}
+
 // ---- random walks and visit counts (kernels_walk.hip) ---------------------------------
 int32_t DGLMIWalkMaxRelations(void) { return walk_max_relations(); }
 int32_t DGLMIWalkStageChunk(void) { return walk_stage_chunk(); }

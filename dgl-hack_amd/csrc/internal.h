@@ -836,6 +836,19 @@ void launch_select_topk(const SampleCsr& c, const int32_t* seeds, int64_t num_se
                         const int64_t* offsets, int64_t num_out, int32_t* out_nbr, int64_t* out_eid,
                         hipStream_t s);
 
+// ordered CSR row-and-column slice (kernels_subgraph.hip): see DGLMICsrSliceCount / Fill.
+// One block per tile of max_pos; keep: ceil(max_pos / 64) words, tile_cnt / tile_scan:
+// subgraph_tiles(max_pos) values.
+int subgraph_tile();
+int64_t subgraph_tiles(int64_t max_pos);
+void launch_slice_count(const SampleCsr& c, const int32_t* nodes, int64_t S, const int64_t* goff,
+                        const int32_t* table, int64_t table_len, int64_t max_pos, uint64_t* keep,
+                        int64_t* tile_cnt, hipStream_t s);
+void launch_slice_fill(const SampleCsr& c, const int32_t* nodes, int64_t S, const int64_t* goff,
+                       const int32_t* table, int64_t table_len, int64_t max_pos,
+                       const uint64_t* keep, const int64_t* tile_scan, int64_t num_out,
+                       int32_t* new_src, int32_t* new_dst, int64_t* parent_eid, hipStream_t s);
+
 // random walks and visit counts (kernels_walk.hip): see DGLMIRandomWalk and DGLMIVisitTopK.
 // The relations' out-CSRs travel by value in the kernel argument: no device allocation.
 constexpr int kWalkMaxRels = 16;

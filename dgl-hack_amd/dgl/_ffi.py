@@ -433,6 +433,15 @@ _SIGS = {
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMISubgraphTile": (ctypes.c_int32, []),
+    "DGLMICsrSliceCount": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    "DGLMICsrSliceFill": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "DGLMIWalkMaxRelations": (ctypes.c_int32, []),
     "DGLMIWalkStageChunk": (ctypes.c_int32, []),
     "DGLMIRandomWalk": (ctypes.c_int, [

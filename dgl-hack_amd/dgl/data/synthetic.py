@@ -9,7 +9,7 @@ formed on the host in fp64; the device draws uniforms from a seeded generator an
 inverts the CDF with a binary search -- both order-independent."""
 import torch as th
 
-__all__ = ["chung_lu_edges"]
+__all__ = ["chung_lu_edges", "planted_cluster_edges"]
 
 
 def chung_lu_edges(n, m, alpha, seed, device):
@@ -30,3 +30,20 @@ def chung_lu_edges(n, m, alpha, seed, device):
         ends.append(th.searchsorted(cdf, u, right=True).clamp_(max=n - 1).to(th.int32))
         del u
     return ends[0], ends[1]
+
+
+def planted_cluster_edges(n, clusters, m, p_in, seed, device):
+    """(src, dst, label): ``m`` int32 device edges over ``n`` nodes in ``clusters`` planted
+    clusters (node v belongs to cluster v mod clusters; ``label`` int64).  An edge stays
+    inside its source's cluster with probability ``p_in`` and goes anywhere otherwise.  The
+    draws come from a seeded host generator, so every process agrees on the graph."""
+    gc = th.Generator().manual_seed(int(seed))
+    src = th.randint(0, n, (m,), generator=gc)
+    anywhere = th.randint(0, n, (m,), generator=gc)
+    inside = th.rand(m, generator=gc) < float(p_in)
+    # a node of the source's cluster: round `anywhere` down to that residue class
+    same = anywhere - anywhere % clusters + src % clusters
+    same = th.where(same >= n, same - clusters, same)
+    dst = th.where(inside, same, anywhere)
+    label = th.arange(n) % clusters
+    return src.to(device, th.int32), dst.to(device, th.int32), label.to(device)

@@ -44,6 +44,11 @@ from .init import zero_initializer
 ALL = "__ALL__"
 
 
+class _NotASubgraph(DGLError, AttributeError):
+    """The reference's DGLError for subgraph bookkeeping asked of a graph without a parent;
+    an AttributeError too, so that ``hasattr(g, "parent_nid")`` answers False."""
+
+
 def is_all(x):
     return isinstance(x, str) and x == ALL
 
@@ -514,6 +519,196 @@ class DGLGraph(object):
         e = self.edge_ids([u], [v])
         return e if return_array or e.shape[0] != 1 else int(e[0])
 
+    # ---- induced subgraphs on the device (graph.py:1375-1600, 3423-3565) ------------
+    def _sub_device(self):
+        from .transform import _built_on
+        dev = _built_on(self._graph)
+        if dev is None:
+            if not th.cuda.is_available():
+                raise DGLError("subgraph: no ROCm device: the MI355X engine runs on ROCm devices only")
+            dev = th.device("cuda", th.cuda.current_device())
+        return dev
+
+    @staticmethod
+    def _ids_1d(ids, what, name):
+        """Reject what ``transform._device_ids`` would flatten: ids must be 1-D."""
+        if (ids.dim() if isinstance(ids, th.Tensor) else np.ndim(ids)) != 1:
+            raise DGLError("%s: %s must be a 1-D list, array or tensor of ids" % (what, name))
+
+    def _make_subgraph(self, src, dst, nid, eid):
+        from .base import NID, EID
+        sg = DGLGraph.from_device_coo(src, dst, int(nid.shape[0]))
+        sg._parent = self
+        sg.ndata[NID] = nid
+        sg.edata[EID] = eid
+        return sg
+
+    def subgraph(self, nodes):
+        """The subgraph induced on ``nodes`` (``graph.py:3423-3472``; a list, a numpy array or
+        a host or device tensor), as a read-only graph on the device.  Node i is
+        ``nodes[i]``; the edges are those of ``nodes[0]``, ``nodes[1]``, .. in out-CSR order
+        whose destination is among ``nodes`` (``CSRSliceMatrix``), parallel edges and self
+        loops included.  ``parent_nid`` / ``parent_eid`` are device int64 ids into this
+        graph.  Built by ``dgl.kernel.csr_slice``; one readback of sizes, no id visits the
+        host.  A repeated node raises, and so does a device id outside the graph.  Batch
+        metadata is not carried over."""
+        from . import kernel as K
+        from .transform import _built_on, _device_ids
+        what, n = "subgraph", self.number_of_nodes()
+        self._ids_1d(nodes, what, "nodes")
+        ids, dev = _device_ids(nodes, n, _built_on(self._graph), what, "nodes")
+        # device ids are checked at their own width: _device_ids narrows them to int32
+        wide = nodes if isinstance(nodes, th.Tensor) and nodes.is_cuda else ids
+        bad = ((wide < 0) | (wide >= n)).sum().reshape(1)
+        csr =self._graph.get_immutable_gidx(dev).out_csr
+        src, dst, eid, distinct, bad = K.csr_slice(csr, ids, extra=bad)
+        if bad:
+            raise DGLError("subgraph: %d of nodes are out of range [0, %d)" % (bad, n))
+        if distinct != ids.shape[0]:
+            raise DGLError("subgraph: nodes repeats a node (%d distinct of %d)"
+                           % (distinct, ids.shape[0]))
+        return self._make_subgraph(src, dst, ids.long(), eid)
+
+    def subgraphs(self, nodes):
+        """One :meth:`subgraph` per node list (``graph.py:3474-3504``)."""
+        return [self.subgraph(v) for v in nodes]
+
+    def edge_subgraph(self, edges, preserve_nodes=False):
+        """The subgraph of the edges ``edges`` (ids; ``graph.py:3506-3565``), edge j being
+        ``edges[j]``.  With ``preserve_nodes`` every node is kept under its own id;
+        otherwise the nodes are the edges' endpoints, numbered by first appearance over all
+        sources, then all destinations (``array_op_impl.cc:162-182``).  The ids are checked
+        on the device (the endpoints are read at clamped ids) and the number of bad ones is
+        read back with the sizes: an id outside the graph raises."""
+        from . import kernel as K
+        what, n, m = "edge_subgraph", self.number_of_nodes(), self.number_of_edges()
+        self._ids_1d(edges, what, "edges")
+        if isinstance(edges, th.Tensor):
+            if edges.is_floating_point() or edges.dtype == th.bool:
+                raise DGLError("%s: edges must hold integers, got %s" % (what, edges.dtype))
+            e = edges.detach()
+        else:
+            host = np.asarray(edges)
+            if host.size and not np.issubdtype(host.dtype, np.integer):
+                raise DGLError("%s: edges must hold integers, got %s" % (what, host.dtype))
+            e = th.from_numpy(host.astype(np.int64))
+        dev = self._sub_device()
+        if e.is_cuda and e.device != dev:
+            raise DGLError("%s: edges is on %s, the graph on %s" % (what, e.device, dev))
+        e = e.to(dev, th.int64)
+        k = int(e.shape[0])
+        if m == 0 and k:
+            raise DGLError("%s: %d edge ids given, the graph has no edge" % (what, k))
+        bad = ((e < 0) | (e >= m)).sum().reshape(1)
+        src, dst = self._graph.get_immutable_gidx(dev).coo()
+        ec = e.clamp(0, max(m - 1, 0))
+        s, d = src[ec], dst[ec]
+        if preserve_nodes:
+            nid = th.arange(n, dtype=th.int64, device=dev)
+            bad = int(bad)
+        else:
+            nid, both, _, bad = K.block_relabel(s[:0], th.cat([s, d]), n, False, extra=bad)
+            s, d = both[:k], both[k:]
+        if bad:
+            raise DGLError("%s: %d edge ids are out of range [0, %d)" % (what, bad, m))
+        return self._make_subgraph(s.contiguous(), d.contiguous(), nid, e)
+
+    @property
+    def parent(self):
+        """The graph this subgraph was cut from; None for any other graph."""
+        return getattr(self, "_parent", None)
+
+    def _check_sub(self, what):
+        if self.parent is None:
+            raise _NotASubgraph("We only support %s for subgraphs." % what)
+
+    @property
+    def parent_nid(self):
+        """Device int64: the parent's id of every node (``graph.py:1375-1394``)."""
+        from .base import NID
+        if "_parent_nid" in self.__dict__:
+            return self.__dict__["_parent_nid"]
+        self._check_sub("parent_nid")
+        return self._node_frame[NID]
+
+    @parent_nid.setter
+    def parent_nid(self, ids):
+        # partition_graph_with_halo attaches the host ids of its parts, which have no parent
+        self.__dict__["_parent_nid"] = ids
+
+    @property
+    def parent_eid(self):
+        """Device int64: the parent's id of every edge (``graph.py:1397-1416``)."""
+        from .base import EID
+        if "_parent_eid" in self.__dict__:
+            return self.__dict__["_parent_eid"]
+        self._check_sub("parent_eid")
+        return self._edge_frame[EID]
+
+    @parent_eid.setter
+    def parent_eid(self, ids):
+        self.__dict__["_parent_eid"] = ids
+
+    def copy_from_parent(self):
+        """Replace the features by the parent's rows ``parent_nid`` / ``parent_eid`` of
+        every parent column (``graph.py:1484-1558``), gathered on the ids' device."""
+        from . import kernel as K
+        from .base import NID, EID
+        self._check_sub("copy_from_parent")
+
+        def take(frame, ids, own):
+            cols = {}
+            for key, v in frame.items():
+                if key == own:
+                    continue
+                if v.device != ids.device:
+                    cols[key] = v[ids.to(v.device)].to(ids.device)
+                elif v.requires_grad:
+                    cols[key] = v[ids]
+                else:
+                    cols[key] = K.gather_rows(v, ids)
+            cols[own] = ids
+            return cols
+
+        ncols = take(self._parent._node_frame, self.parent_nid, NID)
+        ecols = take(self._parent._edge_frame, self.parent_eid, EID)
+        self._node_frame = Frame(self.number_of_nodes, ncols)
+        self._edge_frame = Frame(self.number_of_edges, ecols)
+
+    def copy_to_parent(self, inplace=False):
+        """Write every feature row back to the parent's rows ``parent_nid`` /
+        ``parent_eid`` (``graph.py:1418-1482``; the id columns are not copied).  A column
+        the parent lacks is created from its initializer."""
+        from .base import NID, EID
+        self._check_sub("copy_to_parent")
+        p = self._parent
+        for frame, into, ids, own, rows in (
+                (self._node_frame, p._node_frame, self.parent_nid, NID, p.number_of_nodes()),
+                (self._edge_frame, p._edge_frame, self.parent_eid, EID, p.number_of_edges())):
+            data = {key: v for key, v in frame.items() if key != own}
+            p._rows(into, ids, data, rows, inplace)
+
+    def map_to_subgraph_nid(self, parent_vids):
+        """The subgraph ids of the parent nodes ``parent_vids`` (``graph.py:1560-1595``), as
+        a device int64 tensor: a lookup through a scatter of ``parent_nid``.  An id that is
+        not in the subgraph raises."""
+        from .transform import _device_ids
+        what = "map_to_subgraph_nid"
+        self._check_sub(what)
+        self._ids_1d(parent_vids, what, "parent_vids")
+        nid, n = self.parent_nid, self._parent.number_of_nodes()
+        v, _ = _device_ids(parent_vids, n, nid.device, what, "parent_vids")
+        table = th.full((max(n, 1),), -1, dtype=th.int64, device=nid.device)
+        table[nid] = th.arange(nid.shape[0], dtype=th.int64, device=nid.device)
+        # device ids keep their own width for the check: _device_ids narrows them to int32
+        wide = isinstance(parent_vids, th.Tensor) and parent_vids.is_cuda
+        v = parent_vids.long() if wide else v.long()
+        out = table[v.clamp(0, max(n - 1, 0))]
+        missing = int(((out < 0) | (v < 0) | (v >= n)).sum())
+        if missing:
+            raise DGLError("%s: %d of parent_vids are not in the subgraph" % (what, missing))
+        return out
+
     # ---- feature access by rows (graph.py:1870-2060) -----------------------------
     def _rows(self, frame, sel, data, num_rows, inplace):
         for k, val in data.items():
@@ -685,6 +880,7 @@ class DGLGraph(object):
         g._batch_num_nodes = getattr(self, "_batch_num_nodes", None)
         g._batch_num_edges = getattr(self, "_batch_num_edges", None)
         g._segment_cache = self.__dict__.setdefault("_segment_cache", {})
+        g._parent = getattr(self, "_parent", None)
         for attr in ("_message_func", "_reduce_func", "_apply_node_func", "_apply_edge_func"):
             if hasattr(self, attr):
                 setattr(g, attr, getattr(self, attr))

@@ -1401,6 +1401,72 @@ def _block_relabel(L, dev, table, num_nodes, dst_nodes, S, src, E, inc, flags, s
     return src_nodes[:got[0]], new_src, got[1]
 
 
+# ---- ordered CSR row-and-column slice (DGLGraph.subgraph) ---------------------------------
+def subgraph_tile():
+    """Gathered positions per tile of ``csr_slice`` (DGLMISubgraphTile)."""
+    return int(_ffi.lib().DGLMISubgraphTile())
+
+
+def csr_slice(csr, nodes, extra=None):
+    """The entries of the rows ``nodes[i]`` of ``csr`` (a square DeviceCSR) whose column is
+    among ``nodes`` (device int32), rows in the order given, CSR order within a row ->
+    DGLMICsrSliceCount / Fill, whose header states the result.  Returns (new_src int32,
+    new_dst int32, parent_eid int64, distinct): slots into ``nodes`` and the CSR's data, on
+    the device, and the number of distinct nodes; when it is below ``len(nodes)`` a node
+    repeats and the three tensors are empty.  One readback; ``extra`` (a device int64 tensor
+    of one value) is read back with it and returned as a fifth item.  The device's relabel
+    table is shared: calls on different streams of one device must not overlap."""
+    dev = csr.indptr.device
+    nodes = _ids32(nodes, "nodes", dev)
+    table = relabel_table(dev, max(csr.num_rows, csr.num_cols))
+    try:
+        return _csr_slice(_ffi.lib(), dev, csr, nodes, table, extra)
+    except Exception:
+        _relabel_tables.pop(str(dev), None)  # it may hold marks: the next call starts afresh
+        raise
+
+
+def _csr_slice(L, dev, csr, nodes, table, extra):
+    S, cap, T = int(nodes.shape[0]), csr.nnz, subgraph_tile()
+    tiles = (cap + T - 1) // T
+    c = csr.cstruct()
+    tlen = int(table.shape[0])
+    goff = th.empty(S + 1, dtype=th.int64, device=dev)
+    flags = th.empty(S, dtype=th.int32, device=dev)
+    keep = th.empty((cap + 63) // 64, dtype=th.int64, device=dev)
+    tile_cnt = th.empty(tiles, dtype=th.int64, device=dev)
+    counts = th.empty(2, dtype=th.int64, device=dev)
+    with th.cuda.device(dev):
+        s = _stream(goff)
+        check_call(L.DGLMICsrGatherRows(ctypes.byref(c), csr.bits, _vp(nodes), S, _vp(goff), 0, None,
+                                        None, s))
+        goff = th.cumsum(goff, 0)
+        check_call(L.DGLMIBlockRelabelMark(_vp(table), tlen, _vp(nodes), S, None, 0, 1, _vp(flags), s))
+        scan = th.cumsum(flags, 0, dtype=th.int32)
+        common = (ctypes.byref(c), csr.bits, _vp(nodes), S, _vp(goff), _vp(table), tlen, cap)
+        check_call(L.DGLMICsrSliceCount(*common, _vp(keep), _vp(tile_cnt), s))
+        tile_scan = th.cumsum(tile_cnt, 0)
+        sizes = [tile_scan[-1:], scan[-1:].long()] + ([] if extra is None else [extra])
+        got = [int(v) for v in th.cat(sizes).tolist()]  # the call's one readback
+        total = got[0] if tiles else 0
+        distinct = got[1 if tiles else 0] if S else 0
+        if distinct < S:
+            total = 0
+        new_src = th.empty(total, dtype=th.int32, device=dev)
+        new_dst = th.empty(total, dtype=th.int32, device=dev)
+        eid = th.empty(total, dtype=th.int64, device=dev)
+        if total:
+            check_call(L.DGLMICsrSliceFill(*common, _vp(keep), _vp(tile_scan), total, _vp(new_src),
+                                           _vp(new_dst), _vp(eid), s))
+        # Write stores the sentinel back into the entries Mark lowered; its ids are not needed
+        src_nodes = th.empty(S, dtype=th.int64, device=dev)
+        check_call(L.DGLMIBlockRelabelWrite(_vp(table), tlen, _vp(nodes), S, None, 0, 1, _vp(flags),
+                                            _vp(scan), _vp(src_nodes), None, _vp(counts), s))
+    if extra is not None:
+        return new_src, new_dst, eid, distinct, got[-1]
+    return new_src, new_dst, eid, distinct
+
+
 # ---- random walks and visit counts (dgl.sampling.random_walk, PinSAGESampler) -------------
 def walk_max_relations():
     """The most relations one ``random_walk`` call takes (DGLMIWalkMaxRelations)."""

@@ -1046,6 +1046,58 @@ int DGLMISelectTopk(const DGLMICsr* csr, int32_t num_bits, const int32_t* seeds,
                     int32_t weight_dtype, int64_t* offsets, int64_t num_out, int32_t* out_nbr,
                     int64_t* out_eid, void* stream);
 
+/* ---- ordered CSR row-and-column slice (induced subgraphs) ------------------------
+ * DGLGraph.subgraph: CSR::VertexSubgraph -> aten::CSRSliceMatrix (spmat_op_impl.cc:495-542)
+ * applied to the out-CSR (immutable_graph.cc:219-230, 473-479), with every id kept on the
+ * device.  The result to reproduce, for the S selected nodes nodes[0 .. S - 1]:
+ *   Take the rows nodes[0], nodes[1], .. in the order given and, within a row, the CSR's own
+ *   order.  Keep the entries whose column is among `nodes`.  Kept entry number j is edge j of
+ *   the subgraph: its source is the row's slot i, its destination the column's position in
+ *   `nodes`, its parent edge id the CSR's data[entry].  Parallel edges and self loops are
+ *   entries like any other.  An id outside [0, num_rows) in `nodes` is a row of degree 0 and a
+ *   column that is never matched.
+ * Arguments common to both entries (device arrays unless said otherwise):
+ *   nodes: int32, num_sel entries (0 <= num_sel < 2^31).
+ *   goff: int64, num_sel + 1 values: the running sum of the selected rows' degrees (the count
+ *     phase of DGLMICsrGatherRows, then a running sum).  Gathered position p in [0, goff[num_sel])
+ *     is entry p - goff[i] of row nodes[i], i the last slot with goff[i] <= p; each lane finds
+ *     its slot by a search in goff, so a hub row spreads over many wavefronts.  Positions are
+ *     64-bit.
+ *   table: int32, table_len entries: table[v] = the position of v in `nodes`, INT32_MAX for
+ *     every other v (DGLMIBlockRelabelMark with dst_nodes = nodes and E = 0 leaves exactly
+ *     this; DGLMIBlockRelabelWrite restores it after the slice).  A column outside
+ *     [0, table_len) is not matched.
+ *   max_pos: the capacity the caller sized the work arrays for.  The entries read
+ *     G = min(goff[num_sel], max_pos) on the device, so the host needs no readback to launch
+ *     them; the CSR's nnz bounds goff[num_sel] whenever `nodes` holds no node twice.
+ *   Work is cut into tiles of T = DGLMISubgraphTile() positions (a compile-time constant and a
+ *     multiple of 64; 1024), ceil(max_pos / T) of them.
+ * DGLMICsrSliceCount:
+ *   keep: uint64, ceil(max_pos / 64) words; word w < ceil(G / 64) receives one bit per
+ *     position (bit b = position 64 w + b is kept; the bits of positions >= G are 0).  Words
+ *     from ceil(G / 64) on are not written.
+ *   tile_cnt: int64, ceil(max_pos / T) values: the number of kept positions of every tile
+ *     (0 for a tile that starts at or after G).
+ * The caller turns tile_cnt into its inclusive running sum tile_scan; its last value is the
+ *   number of subgraph edges, read back (with the distinct-node count of the relabel's
+ *   flags) to size the outputs: the call's one readback.
+ * DGLMICsrSliceFill reads the bitmap for membership, not the table.  The output rank of a
+ *   kept position is tile_scan[t - 1] (0 for t = 0), plus the popcounts of the earlier words
+ *   of its tile, plus the number of lower set bits of its own word.  It writes
+ *     new_src[rank] = slot (int32), new_dst[rank] = table[col] (int32),
+ *     parent_eid[rank] = data[entry] (int64),
+ *   and drops writes outside [0, num_out).
+ * num_bits: 32, or 64 when indptr / data hold int64 values.  No atomics and no float
+ * arithmetic take part: the same bits on every run. */
+int32_t DGLMISubgraphTile(void);
+int DGLMICsrSliceCount(const DGLMICsr* csr, int32_t num_bits, const int32_t* nodes, int64_t num_sel,
+                       const int64_t* goff, const int32_t* table, int64_t table_len,
+                       int64_t max_pos, uint64_t* keep, int64_t* tile_cnt, void* stream);
+int DGLMICsrSliceFill(const DGLMICsr* csr, int32_t num_bits, const int32_t* nodes, int64_t num_sel,
+                      const int64_t* goff, const int32_t* table, int64_t table_len, int64_t max_pos,
+                      const uint64_t* keep, const int64_t* tile_scan, int64_t num_out,
+                      int32_t* new_src, int32_t* new_dst, int64_t* parent_eid, void* stream);
+
 /* ---- random walks and visit counts ------------------------------------------
  * dgl.sampling.random_walk and the counting step of RandomWalkNeighborSampler /
  * PinSAGESampler (_CAPI_DGLSamplingRandomWalk, ..WithRestart, ..WithStepwiseRestart;
