@@ -3155,6 +3155,109 @@ int DGLMICsrSliceFill(const DGLMICsr* csr, int32_t num_bits, const int32_t* node
   API_END();
 }
 
+// ---- ordered BFS / topological frontiers (kernels_traverse.hip) -----------------------
+int32_t DGLMITraverseTile(void) { return traverse_tile(); }
+int32_t DGLMITraverseNarrowLimit(void) { return traverse_narrow_limit(); }
+int32_t DGLMITraverseMaxLevelsPerLaunch(void) { return traverse_max_levels(); }
+
+namespace {
+
+// the workspace's arrays, each 8-byte aligned; returns the bytes used
+int64_t traverse_carve(int64_t N, int64_t nnz, int64_t num_sources, int32_t num_bits, char* base,
+                       TraverseBuffers* b) {
+  int64_t at = 0;
+  auto take = [&](int64_t bytes) {
+    char* p = base != nullptr ? base + at : nullptr;  // null base: sizes only
+    at += (bytes + 7) / 8 * 8;
+    return p;
+  };
+  const int64_t T = traverse_tile();
+  b->cap_sections = N + 2;
+  b->cap_q = N + num_sources;
+  b->cap_pos = N > nnz ? N : nnz;
+  b->st = reinterpret_cast<int64_t*>(take(kTraverseStateWords * 8));
+  b->sections = reinterpret_cast<int64_t*>(take(b->cap_sections * 8));
+  b->gq = reinterpret_cast<int64_t*>(take(b->cap_q * 8));
+  b->key = take(N * (num_bits == 64 ? 8 : 4));
+  b->visited = reinterpret_cast<uint32_t*>(take((N + 31) / 32 * 4));
+  b->rem = reinterpret_cast<int32_t*>(take(N * 4));
+  b->keep = reinterpret_cast<uint64_t*>(take((b->cap_pos + 63) / 64 * 8));
+  b->tile_cnt = reinterpret_cast<int64_t*>(take((b->cap_pos + T - 1) / T * 8));
+  return at;
+}
+
+TraverseBuffers traverse_buffers(const DGLMICsr* csr, int32_t num_bits, int32_t kind,
+                                 int64_t num_sources, int32_t* ids, int64_t* eids, int64_t num_eids,
+                                 void* workspace, int64_t workspace_bytes) {
+  DGLMI_CHECK(kind >= kTraverseBfsNodes && kind <= kTraverseTopo,
+              "traverse: kind must be 0 (BFS nodes), 1 (BFS edges) or 2 (topological)");
+  DGLMI_CHECK(num_sources >= 0 && num_sources < (int64_t(1) << 31), "traverse: bad source count");
+  DGLMI_CHECK(kind != kTraverseTopo || num_sources == 0, "traverse: topological order takes no source");
+  DGLMI_CHECK(csr->num_rows == csr->num_cols, "traverse: the graph must be square");
+  DGLMI_CHECK(ids != nullptr && workspace != nullptr, "traverse: null ids or workspace");
+  DGLMI_CHECK(num_eids >= 0 && (kind != kTraverseBfsEdges || num_eids == 0 || eids != nullptr),
+              "traverse: null eids");
+  TraverseBuffers b{};
+  const int64_t need = traverse_carve(csr->num_rows, csr->nnz, num_sources, num_bits,
+                                      static_cast<char*>(workspace), &b);
+  DGLMI_CHECK(workspace_bytes >= need, "traverse: workspace too small: " +
+                                           std::to_string(workspace_bytes) + " < " + std::to_string(need));
+  DGLMI_CHECK(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "traverse: workspace not 8-byte aligned");
+  b.q = ids;
+  b.eids = kind == kTraverseBfsEdges ? eids : nullptr;
+  b.cap_e = kind == kTraverseBfsEdges ? num_eids : 0;
+  return b;
+}
+
+}  // namespace
+
+int64_t DGLMITraverseWorkspaceBytes(int64_t num_nodes, int64_t nnz, int64_t num_sources,
+                                    int32_t num_bits) {
+  if (num_nodes < 0 || nnz < 0 || num_sources < 0) return -1;
+  TraverseBuffers b{};
+  return traverse_carve(num_nodes, nnz, num_sources, num_bits, nullptr, &b);
+}
+
+int DGLMITraverseInit(const DGLMICsr* csr, const DGLMICsr* opposite, int32_t num_bits, int32_t kind,
+                      const int32_t* source, int64_t num_sources, int32_t* ids, int64_t* eids,
+                      int64_t num_eids, void* workspace, int64_t workspace_bytes, void* stream) {
+  API_BEGIN();
+  const SampleCsr c = sample_csr(csr, num_bits);
+  const TraverseBuffers b = traverse_buffers(csr, num_bits, kind, num_sources, ids, eids, num_eids,
+                                             workspace, workspace_bytes);
+  DGLMI_CHECK(num_sources == 0 || source != nullptr, "traverse: null source");
+  IdxPtr opp{nullptr, 0};
+  if (kind == kTraverseTopo) {
+    const SampleCsr o = sample_csr(opposite, num_bits);
+    DGLMI_CHECK(o.num_rows == c.num_rows, "traverse: the opposite CSR has another node count");
+    opp = o.indptr;
+  }
+  DeviceGuard guard(device_of(workspace, "traverse workspace: not a device pointer"));
+  launch_traverse_init(c, opp, kind, source, num_sources, b, static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "traverse init launch");
+  API_END();
+}
+
+int DGLMITraverseStep(const DGLMICsr* csr, int32_t num_bits, int32_t kind, int32_t variant,
+                      int64_t num_front, int64_t num_pos, int64_t num_sources, int32_t* ids,
+                      int64_t* eids, int64_t num_eids, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(variant >= 0 && variant <= 2, "traverse: variant must be 0, 1 or 2");
+  const SampleCsr c = sample_csr(csr, num_bits);
+  const TraverseBuffers b = traverse_buffers(csr, num_bits, kind, num_sources, ids, eids, num_eids,
+                                             workspace, workspace_bytes);
+  DGLMI_CHECK(num_front >= 0 && num_front <= b.cap_q && num_pos >= 0 && num_pos <= b.cap_pos,
+              "traverse: the frontier does not fit the workspace");
+  // the shipped choice takes the narrow route wherever it is legal
+  const int64_t limit = traverse_narrow_limit();
+  const bool narrow = variant != 1 && num_front <= limit && num_pos <= limit;
+  DeviceGuard guard(device_of(workspace, "traverse workspace: not a device pointer"));
+  launch_traverse_step(c, kind, narrow, num_pos, b, static_cast<hipStream_t>(stream));
+  check_hip(hipGetLastError(), "traverse step launch");
+  API_END();
+}
+
 // ---- random walks and visit counts (kernels_walk.hip) ---------------------------------
 int32_t DGLMIWalkMaxRelations(void) { return walk_max_relations(); }
 int32_t DGLMIWalkStageChunk(void) { return walk_stage_chunk(); }

@@ -876,4 +876,38 @@ void launch_visit_topk(const int64_t* traces, int64_t row_len, int64_t num_seeds
                        int64_t walks_per_seed, int64_t col0, int64_t col_step, int ncols, int K,
                        int32_t* out_nbr, int32_t* out_cnt, int32_t* out_num, hipStream_t s);
 
+// ordered BFS / topological frontiers (kernels_traverse.hip): see DGLMITraverseInit / Step.
+// The level state's words (DGLMI_TRAVERSE_* in dglmi.h) and the caller's workspace, carved
+// by capi.cpp.
+constexpr int kTraverseBfsNodes = 0, kTraverseBfsEdges = 1, kTraverseTopo = 2;
+constexpr int kTraverseStateWords = 16;
+constexpr int kTravHead = 0, kTravTail = 1, kTravLevel = 2, kTravG = 3, kTravDone = 4, kTravBad = 5,
+              kTravSources = 6, kTravCnt = 7;
+struct TraverseBuffers {
+  int64_t* st;        // kTraverseStateWords
+  int64_t* sections;  // cap_sections
+  int64_t cap_sections;
+  int32_t* q;         // the queue (the caller's ids), cap_q
+  int64_t* gq;        // cap_q: the frontier's running degrees, parallel to q
+  int64_t cap_q;
+  int64_t* eids;      // BFS edges: cap_e
+  int64_t cap_e;
+  void* key;          // num_rows keys: int32, int64 for a 64-bit CSR
+  uint32_t* visited;  // ceil(num_rows / 32)
+  int32_t* rem;       // num_rows
+  uint64_t* keep;     // ceil(cap_pos / 64)
+  int64_t* tile_cnt;  // ceil(cap_pos / traverse_tile())
+  int64_t cap_pos;    // max(num_rows, nnz)
+};
+int traverse_tile();
+int traverse_narrow_limit();
+int traverse_max_levels();
+void launch_traverse_init(const SampleCsr& c, const IdxPtr& opp_indptr, int kind,
+                          const int32_t* source, int64_t num_sources, const TraverseBuffers& b,
+                          hipStream_t s);
+// narrow: one workgroup, up to traverse_max_levels() levels; else one wide level over
+// num_pos = the state's G as the caller read it back
+void launch_traverse_step(const SampleCsr& c, int kind, bool narrow, int64_t num_pos,
+                          const TraverseBuffers& b, hipStream_t s);
+
 }  // namespace dglmi

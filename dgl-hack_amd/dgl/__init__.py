@@ -26,6 +26,11 @@ from .transform import (laplacian_lambda_max, add_self_loop, remove_self_loop,  
                         to_block, in_subgraph, out_subgraph)
 from . import transform  # noqa: F401
 from . import sampling  # noqa: F401
+from . import traversal  # noqa: F401
+from . import propagate  # noqa: F401
+from .traversal import (bfs_nodes_generator, bfs_edges_generator,  # noqa: F401
+                        topological_nodes_generator)
+from .propagate import prop_nodes, prop_edges, prop_nodes_bfs, prop_nodes_topo  # noqa: F401
 from . import data  # noqa: F401
 from . import nn  # noqa: F401
 

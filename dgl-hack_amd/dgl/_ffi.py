@@ -442,6 +442,19 @@ _SIGS = {
         ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "DGLMITraverseTile": (ctypes.c_int32, []),
+    "DGLMITraverseNarrowLimit": (ctypes.c_int32, []),
+    "DGLMITraverseMaxLevelsPerLaunch": (ctypes.c_int32, []),
+    "DGLMITraverseWorkspaceBytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int32]),
+    "DGLMITraverseInit": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p]),
+    "DGLMITraverseStep": (ctypes.c_int, [
+        ctypes.POINTER(CSR), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "DGLMIWalkMaxRelations": (ctypes.c_int32, []),
     "DGLMIWalkStageChunk": (ctypes.c_int32, []),
     "DGLMIRandomWalk": (ctypes.c_int, [

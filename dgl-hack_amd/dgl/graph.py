@@ -1162,6 +1162,20 @@ class DGLGraph(object):
         self._partial_reduce(src, dst, eid, message_func, reduce_func, apply_node_func, dst,
                              inplace)
 
+    def prop_nodes(self, nodes_generator, message_func="default", reduce_func="default",
+                   apply_node_func="default"):
+        """:meth:`pull` on every node frontier of ``nodes_generator`` in turn
+        (``graph.py:3266-3340``); the frontiers of ``dgl.traversal`` are device tensors."""
+        for frontier in nodes_generator:
+            self.pull(frontier, message_func, reduce_func, apply_node_func)
+
+    def prop_edges(self, edges_generator, message_func="default", reduce_func="default",
+                   apply_node_func="default"):
+        """:meth:`send_and_recv` on every edge frontier of ``edges_generator`` in turn
+        (``graph.py:3342-3420``)."""
+        for frontier in edges_generator:
+            self.send_and_recv(frontier, message_func, reduce_func, apply_node_func)
+
     def push(self, u, message_func="default", reduce_func="default", apply_node_func="default",
              inplace=False):
         """Send messages along the out-edges of ``u`` and reduce on their destinations

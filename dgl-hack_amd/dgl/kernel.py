@@ -1467,6 +1467,69 @@ def _csr_slice(L, dev, csr, nodes, table, extra):
     return new_src, new_dst, eid, distinct
 
 
+# ---- ordered BFS / topological frontiers (dgl.traversal) ----------------------------------
+TRAVERSE_BFS_NODES, TRAVERSE_BFS_EDGES, TRAVERSE_TOPO = 0, 1, 2
+
+
+def traverse_tile():
+    """Gathered positions per tile of the wide route (DGLMITraverseTile)."""
+    return int(_ffi.lib().DGLMITraverseTile())
+
+
+def traverse_narrow_limit():
+    """The most frontier rows and positions of a narrow level (DGLMITraverseNarrowLimit)."""
+    return int(_ffi.lib().DGLMITraverseNarrowLimit())
+
+
+def traverse_max_levels_per_launch():
+    """Levels one narrow launch runs at most (DGLMITraverseMaxLevelsPerLaunch)."""
+    return int(_ffi.lib().DGLMITraverseMaxLevelsPerLaunch())
+
+
+def traverse(csr, opposite_csr, kind, source, variant=0):
+    """The ordered frontiers of a traversal over ``csr`` (a square DeviceCSR; the out-CSR,
+    or the in-CSR for a reversed traversal) -> DGLMITraverseInit / Step, whose header states
+    the result.  ``kind``: TRAVERSE_BFS_NODES, TRAVERSE_BFS_EDGES or TRAVERSE_TOPO (which
+    reads the degrees of ``opposite_csr`` and takes ``source`` None).  ``source``: device
+    int32 ids.  Returns (ids, sections): a device int64 tensor of node ids (edge ids for
+    TRAVERSE_BFS_EDGES), frontier after frontier, and the frontiers' sizes as a list.  One
+    readback of the level state per step, one of the sections at the end; no id visits the
+    host.  Raises DGLError for a source outside the graph and for a topological traversal
+    that a loop stops."""
+    L = _ffi.lib()
+    dev = csr.indptr.device
+    n, nnz = csr.num_rows, csr.nnz
+    topo = kind == TRAVERSE_TOPO
+    source = None if topo else _ids32(source, "source", dev)
+    ns = 0 if topo else int(source.shape[0])
+    ne = min(n, nnz) if kind == TRAVERSE_BFS_EDGES else 0
+    ids = th.empty(n + ns, dtype=th.int32, device=dev)
+    eids = th.empty(ne, dtype=th.int64, device=dev)
+    nbytes = int(L.DGLMITraverseWorkspaceBytes(n, nnz, ns, csr.bits))
+    ws = th.empty(nbytes // 8, dtype=th.int64, device=dev)
+    c, o = csr.cstruct(), (opposite_csr if topo else csr).cstruct()
+    tail = (_vp(ids), _vp(eids), ne, _vp(ws), nbytes)
+    with th.cuda.device(dev):
+        s = _stream(ws)
+        check_call(L.DGLMITraverseInit(ctypes.byref(c), ctypes.byref(o), csr.bits, kind, _vp(source),
+                                       ns, *tail, s))
+        while True:
+            head, end, level, num_pos, done, bad = ws[:6].tolist()  # the step's one readback
+            if bad:
+                raise DGLError("traverse: %d of the source nodes are out of range [0, %d)" % (bad, n))
+            if done:
+                break
+            check_call(L.DGLMITraverseStep(ctypes.byref(c), csr.bits, kind, int(variant), end - head,
+                                           num_pos, ns, *tail, s))
+        sections = ws[16:16 + level].tolist()
+    if topo and end < n:
+        raise DGLError("traverse: topological order lists %d of %d nodes: there is a loop in the "
+                       "graph" % (end, n))
+    if kind == TRAVERSE_BFS_EDGES:
+        return eids[:end - ns], sections[1:]
+    return ids[:end].long(), sections
+
+
 # ---- random walks and visit counts (dgl.sampling.random_walk, PinSAGESampler) -------------
 def walk_max_relations():
     """The most relations one ``random_walk`` call takes (DGLMIWalkMaxRelations)."""

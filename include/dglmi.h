@@ -1098,6 +1098,81 @@ int DGLMICsrSliceFill(const DGLMICsr* csr, int32_t num_bits, const int32_t* node
                       const uint64_t* keep, const int64_t* tile_scan, int64_t num_out,
                       int32_t* new_src, int32_t* new_dst, int64_t* parent_eid, void* stream);
 
+/* ---- ordered graph traversal: BFS and topological frontiers ---------------------
+ * dgl.traversal.bfs_nodes_generator, bfs_edges_generator and topological_nodes_generator
+ * (_CAPI_DGLBFSNodes, _CAPI_DGLBFSEdges, _CAPI_DGLTopologicalNodes; src/graph/traversal.h
+ * BFSNodes / BFSEdges / TopologicalNodes) with every id kept on the device.  The reference
+ * runs a sequential queue; its frontiers list nodes in the order that queue discovers them,
+ * and that order is the result to reproduce, with no sort.
+ *
+ * The walked CSR is the out-CSR of a forward traversal and the in-CSR of a reversed one; it is
+ * square (N = num_rows nodes), its data holds the edge ids, and a row's entries are taken in
+ * the CSR's own order (an out-CSR row keeps insertion order; an in-CSR row lists sources
+ * ascending and edge ids ascending within a source).  Node ids are int32, positions 64-bit.
+ * Gathered positions.  A frontier is F = f[0 .. S-1].  Its gathered positions p = 0 .. G-1 run
+ *   through row(f[0]), then row(f[1]), .., each row in CSR order; col(p) is the entry's column
+ *   and eid(p) its data.  G may reach nnz and stays exact on 64-bit graphs.  In frontier 0 of
+ *   a BFS a node that an earlier slot already holds contributes no positions: its row was
+ *   gathered at smaller positions, so none of its entries can be a first occurrence.
+ * BFS (kind 0 = nodes, 1 = edges).  Frontier 0 is `source` verbatim, duplicates included, and
+ *   every source is marked visited.  Frontier k+1 is every v = col(p) that was not visited
+ *   before level k, taken once, at the smallest p at which it occurs, in ascending order of
+ *   that p.  The edge variant lists eid(p) of the same winning positions in eids (it has no
+ *   section for the sources: section k of eids is frontier k+1).  Traversal stops at the first
+ *   empty frontier, which is not reported; an empty source gives no frontier.  Sources
+ *   outside [0, N) are counted in the state's BAD word and the traversal does not start.
+ * Topological (kind 2; num_sources = 0).  remaining[v] is v's degree in the opposite CSR (the
+ *   in-degree for a forward traversal; a node's degree must be below 2^31).  Frontier 0 is the
+ *   nodes with remaining == 0, ascending.  At level k every position decrements
+ *   remaining[col(p)], parallel edges once each.  Frontier k+1 is the nodes whose remaining
+ *   is 0 after the level and was not before, ordered by the largest p of the level that
+ *   points at them: where the sequential loop's last decrement lands.  When the traversal
+ *   ends with TAIL < N the graph has a loop (a self loop is one); the caller reports it.
+ * Buffers (device).  ids: int32, N + num_sources entries: the queue itself, frontier after
+ *   frontier.  eids: int64, num_eids entries (kind 1; min(N, nnz) suffices).  workspace: at
+ *   least DGLMITraverseWorkspaceBytes(N, nnz, num_sources, num_bits) bytes, 8-byte aligned,
+ *   one allocation that the same arguments carve the same way in every call; the entries
+ *   allocate nothing.  It starts with the level state, DGLMI_TRAVERSE_STATE_WORDS int64
+ *   words -- HEAD and TAIL (the current frontier is ids[HEAD .. TAIL)), LEVEL (frontiers
+ *   reported so far), G (its gathered positions), DONE, BAD -- followed by the N + 2 int64
+ *   section sizes, of which the first LEVEL are valid.
+ * DGLMITraverseInit writes frontier 0 and the state.  The caller then reads the state back
+ *   (one readback per call) and, while DONE == 0, calls DGLMITraverseStep with
+ *   num_front = TAIL - HEAD and num_pos = G as read.  A step takes one of two routes:
+ *   wide: one level.  Positions are cut into tiles of T = DGLMITraverseTile() (1024, a
+ *     multiple of 64); each lane finds its row by a search in the frontier's running degree
+ *     sum, so a hub row spreads over many wavefronts.  A claim pass does atomicMin(key[v], p)
+ *     on unvisited v (topological: a decrement pass, then atomicMax(key[v], p) where
+ *     remaining[v] == 0, so a key is touched at one level only and is never reset); a count
+ *     pass ballots the positions with key[col(p)] == p into a bitmap with per-tile counts; a
+ *     single workgroup sums the tile counts; a fill pass ranks by popcounts and writes
+ *     ids[TAIL + rank].  No workgroup waits on another.
+ *   narrow: legal while num_front and num_pos are at most DGLMITraverseNarrowLimit() (4096,
+ *     a multiple of T).  One workgroup runs the whole level, then goes on to the next level
+ *     in the same launch; it returns when the frontier is empty, when a frontier exceeds the
+ *     limit (that level is left to the wide route), or after
+ *     DGLMITraverseMaxLevelsPerLaunch() (128) levels: a bounded loop.
+ *   variant: 0 = the shipped choice (narrow wherever legal), 1 = wide only, 2 = narrow
+ *     wherever legal.  The variants differ in speed only.
+ * Keys are int32 when num_bits is 32 (nnz < 2^31) and int64 otherwise.  Only integer atomics
+ * (min, max, add, or) and no float arithmetic take part, and min / max / add commute: the
+ * same bits on every run and for every route. */
+#define DGLMI_TRAVERSE_STATE_WORDS 16
+enum DGLMITraverseState { DGLMI_TRAVERSE_HEAD = 0, DGLMI_TRAVERSE_TAIL = 1, DGLMI_TRAVERSE_LEVEL = 2,
+                          DGLMI_TRAVERSE_G = 3, DGLMI_TRAVERSE_DONE = 4, DGLMI_TRAVERSE_BAD = 5 };
+int32_t DGLMITraverseTile(void);
+int32_t DGLMITraverseNarrowLimit(void);
+int32_t DGLMITraverseMaxLevelsPerLaunch(void);
+int64_t DGLMITraverseWorkspaceBytes(int64_t num_nodes, int64_t nnz, int64_t num_sources,
+                                    int32_t num_bits);
+int DGLMITraverseInit(const DGLMICsr* csr, const DGLMICsr* opposite, int32_t num_bits, int32_t kind,
+                      const int32_t* source, int64_t num_sources, int32_t* ids, int64_t* eids,
+                      int64_t num_eids, void* workspace, int64_t workspace_bytes, void* stream);
+int DGLMITraverseStep(const DGLMICsr* csr, int32_t num_bits, int32_t kind, int32_t variant,
+                      int64_t num_front, int64_t num_pos, int64_t num_sources, int32_t* ids,
+                      int64_t* eids, int64_t num_eids, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
 /* ---- random walks and visit counts ------------------------------------------
  * dgl.sampling.random_walk and the counting step of RandomWalkNeighborSampler /
  * PinSAGESampler (_CAPI_DGLSamplingRandomWalk, ..WithRestart, ..WithStepwiseRestart;
