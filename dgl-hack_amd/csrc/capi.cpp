@@ -2620,6 +2620,229 @@ int DGLMIRgcnRelease(DGLMIRgcnState* state) {
   API_END();
 }
 
+// ---- block-diagonal R-GCN for many relations (kernels_rgcn_bdd.hip) -----------------
+int DGLMIRgcnBddOk(int64_t in_feat, int64_t out_feat, int64_t num_bases) {
+  return dglmi::rgcn_bdd_ok(in_feat, out_feat, num_bases) ? 1 : 0;
+}
+int64_t DGLMIRgcnBddChunk(void) { return kBddChunk; }
+int64_t DGLMIRgcnBddWgradChunk(void) { return kBddWgradChunk; }
+
+int DGLMIRgcnBddPrepare(const DGLMIGraph* graph, const DGLMIArray* norm, int32_t num_rels,
+                        DGLMIRgcnBddState* state, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(state != nullptr, "null state");
+  std::memset(state, 0, sizeof(*state));
+  DGLMI_CHECK(num_rels >= 1, "num_rels must be >= 1");
+  rgcn_common(graph, 0);
+  const DGLMICsr& in = graph->in_csr;
+  const DGLMICsr& out = graph->out_csr;
+  const int64_t R = num_rels, E = in.nnz;
+  if (norm != nullptr) edge_values(norm, E, "norm");
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one allocation, carved into 256-byte aligned arrays: 11 per edge, 2 per relation
+  auto al = [](int64_t bytes) { return (bytes + 255) & ~int64_t(255); };
+  const int64_t e4 = al((E + 1) * 4), r4 = al((R + 1) * 4);
+  struct Owner {
+    void* p = nullptr;
+    ~Owner() { if (p) (void)hipFree(p); }
+  } own;
+  check_hip(hipMalloc(&own.p, static_cast<size_t>(11 * e4 + 2 * r4)), "hipMalloc");
+  char* cur = static_cast<char*>(own.p);
+  auto take = [&](int64_t bytes) { char* r = cur; cur += bytes; return reinterpret_cast<int32_t*>(r); };
+  BddBuild bi{in.indices, in.data, in.rows, graph->etypes, in.num_rows, E, R,
+              take(e4), take(e4), take(e4), take(e4), take(e4), take(e4), take(r4), take(r4)};
+  BddBuild bo{out.indices, out.data, out.rows, graph->etypes, out.num_rows, E, R,
+              take(e4), take(e4), take(e4), nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* in_norm = reinterpret_cast<float*>(take(e4));
+  float* out_norm = reinterpret_cast<float*>(take(e4));
+  if (E == 0) {  // no segments: every relation's lists are empty
+    launch_fill_i32(bi.rel_seg, R + 1, 0, s);
+    launch_fill_i32(bi.chunk_ptr, R + 1, 0, s);
+    launch_fill_i32(bi.seg_first, 1, 0, s);
+  }
+  check_hip(rgcn_bdd_build(bi, s), "bdd state (in-CSR)");
+  check_hip(rgcn_bdd_build(bo, s), "bdd state (out-CSR)");
+  if (norm != nullptr) {
+    launch_rgcn_bdd_norm(norm->data, bi.eid, E, in_norm, s);
+    launch_rgcn_bdd_norm(norm->data, bo.eid, E, out_norm, s);
+  }
+  check_hip(hipGetLastError(), "bdd prepare launch");
+  // the weight gradient's grid and workspace: a count, read back once per state
+  int32_t chunks = 0;
+  check_hip(hipMemcpyAsync(&chunks, bi.chunk_ptr + R, sizeof(chunks), hipMemcpyDeviceToHost, s),
+            "hipMemcpyAsync");
+  check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
+  state->etypes = graph->etypes;
+  state->norm = norm ? norm->data : nullptr;
+  state->num_rels = num_rels;
+  state->nnz = E;
+  state->in_cols = bi.cols;
+  state->in_rel = bi.rel;
+  state->in_eid = bi.eid;
+  state->in_norm = in_norm;
+  state->out_cols = bo.cols;
+  state->out_rel = bo.rel;
+  state->out_eid = bo.eid;
+  state->out_norm = out_norm;
+  state->seg_pos = bi.seg_pos;
+  state->seg_row = bi.seg_row;
+  state->seg_first = bi.seg_first;
+  state->rel_seg = bi.rel_seg;
+  state->chunk_ptr = bi.chunk_ptr;
+  state->num_chunks = chunks;
+  state->owner = own.p;
+  own.p = nullptr;  // the state owns it now
+  API_END();
+}
+
+int DGLMIRgcnBddRefreshNorm(const DGLMIArray* norm, DGLMIRgcnBddState* state, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(state != nullptr && state->owner != nullptr, "state is not prepared");
+  edge_values(norm, state->nnz, "norm");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_rgcn_bdd_norm(norm->data, state->in_eid, state->nnz, state->in_norm, s);
+  launch_rgcn_bdd_norm(norm->data, state->out_eid, state->nnz, state->out_norm, s);
+  check_hip(hipGetLastError(), "bdd refresh norm launch");
+  state->norm = norm->data;
+  API_END();
+}
+
+int DGLMIRgcnBddRelease(DGLMIRgcnBddState* state) {
+  API_BEGIN();
+  if (state != nullptr) {
+    if (state->owner != nullptr) check_hip(hipFree(state->owner), "hipFree");
+    std::memset(state, 0, sizeof(*state));
+  }
+  API_END();
+}
+
+}  // extern "C"
+
+namespace {
+// shapes of a bdd call: x (N_src, in), weight (R, B s_i s_o), rows of `dst` (N_dst, out)
+struct BddShape {
+  int64_t in, out, si, so;
+  int nb;
+};
+BddShape bdd_check(const DGLMIGraph* graph, const DGLMIRgcnBddState* st, const DGLMIArray* x,
+                   const DGLMIArray* weight, int32_t num_bases, const DGLMIArray* norm,
+                   const DGLMIArray* dst, const char* dst_name) {
+  DGLMI_CHECK(st != nullptr && st->owner != nullptr, "state is not prepared");
+  rgcn_common(graph, 0);
+  check_array(x, "x");
+  check_array(weight, "weight");
+  check_array(dst, dst_name);
+  DGLMI_CHECK(st->nnz == graph->in_csr.nnz, "the graph is not the state's");
+  DGLMI_CHECK(x->ndim == 2 && dst->ndim == 2 && weight->ndim == 2, "x, weight and the output are 2-D");
+  DGLMI_CHECK(x->shape[0] == graph->in_csr.num_cols, "x needs one row per source node");
+  DGLMI_CHECK(dst->shape[0] == graph->in_csr.num_rows,
+              std::string(dst_name) + " needs one row per destination node");
+  DGLMI_CHECK(weight->shape[0] == st->num_rels, "weight needs one row per relation of the state");
+  BddShape sh{x->shape[1], dst->shape[1], 0, 0, num_bases};
+  DGLMI_CHECK(rgcn_bdd_ok(sh.in, sh.out, num_bases), "unsupported bdd shape (DGLMIRgcnBddOk)");
+  sh.si = sh.in / num_bases;
+  sh.so = sh.out / num_bases;
+  DGLMI_CHECK(weight->shape[1] == num_bases * sh.si * sh.so, "weight must be (R, B * s_i * s_o)");
+  DGLMI_CHECK(norm == nullptr || (st->norm != nullptr && norm->data == st->norm),
+              "norm is not the state's (DGLMIRgcnBddRefreshNorm first)");
+  return sh;
+}
+
+// the walk over one regrouped CSR with its carries
+void bdd_walk(bool transposed, const DGLMICsr& c, const int32_t* cols, const int32_t* rel,
+              const float* norm, const float* x, const float* W, const BddShape& sh, float* out,
+              const float* bias, const float* addend, hipStream_t s) {
+  BddArgs a{};
+  a.indptr = c.indptr;
+  a.rows = c.rows;
+  a.cols = cols;
+  a.rel = rel;
+  a.norm = norm;
+  a.num_rows = c.num_rows;
+  a.nnz = c.nnz;
+  a.x = x;
+  a.W = W;
+  a.out = out;
+  a.wi = transposed ? sh.out : sh.in;
+  a.wo = transposed ? sh.in : sh.out;
+  a.nb = sh.nb;
+  a.si = static_cast<int>(sh.si);
+  a.so = static_cast<int>(sh.so);
+  a.bias = bias;
+  a.addend = addend;
+  a.chunk = kBddChunk;
+  const CarryLayout lay(rgcn_bdd_chunks(c.nnz), a.wo);
+  Scratch ws(no_workspace(), lay.bytes, s);
+  lay.point(a, ws.ptr);
+  launch_rgcn_bdd(transposed, a, s);
+  check_hip(hipGetLastError(), "bdd walk launch");
+}
+}  // namespace
+
+extern "C" {
+
+int DGLMIRgcnBddForward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state,
+                        const DGLMIArray* x, const DGLMIArray* weight, int32_t num_bases,
+                        const DGLMIArray* norm, const float* bias, const float* addend,
+                        DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  const BddShape sh = bdd_check(graph, state, x, weight, num_bases, norm, out, "out");
+  DGLMI_CHECK(addend == nullptr || addend != out->data, "addend must not alias out");
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  bdd_walk(false, graph->in_csr, state->in_cols, state->in_rel, norm ? state->in_norm : nullptr,
+           x->data, weight->data, sh, out->data, bias, addend, s);
+  API_END();
+}
+
+int DGLMIRgcnBddBackward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state,
+                         const DGLMIArray* x, const DGLMIArray* weight, int32_t num_bases,
+                         const DGLMIArray* norm, const DGLMIArray* grad_out, DGLMIArray* grad_x,
+                         DGLMIArray* grad_weight, void* stream) {
+  API_BEGIN();
+  const BddShape sh = bdd_check(graph, state, x, weight, num_bases, norm, grad_out, "grad_out");
+  DGLMI_CHECK(graph->out_csr.num_rows == graph->in_csr.num_cols, "out_csr rows != in_csr columns");
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (grad_x != nullptr) {
+    check_array(grad_x, "grad_x");
+    DGLMI_CHECK(grad_x->ndim == 2 && grad_x->shape[0] == x->shape[0] && grad_x->shape[1] == sh.in,
+                "grad_x must have x's shape");
+    bdd_walk(true, graph->out_csr, state->out_cols, state->out_rel,
+             norm ? state->out_norm : nullptr, grad_out->data, weight->data, sh, grad_x->data,
+             nullptr, nullptr, s);
+  }
+  if (grad_weight != nullptr) {
+    check_array(grad_weight, "grad_weight");
+    DGLMI_CHECK(grad_weight->ndim == 2 && grad_weight->shape[0] == weight->shape[0] &&
+                    grad_weight->shape[1] == weight->shape[1],
+                "grad_weight must have weight's shape");
+    BddWgradArgs a{};
+    a.seg_pos = state->seg_pos;
+    a.seg_row = state->seg_row;
+    a.seg_first = state->seg_first;
+    a.rel_seg = state->rel_seg;
+    a.chunk_ptr = state->chunk_ptr;
+    a.R = state->num_rels;
+    a.num_chunks = state->num_chunks;
+    a.cols = state->in_cols;
+    a.norm = norm ? state->in_norm : nullptr;
+    a.x = x->data;
+    a.g = grad_out->data;
+    a.fi = sh.in;
+    a.fo = sh.out;
+    a.si = static_cast<int>(sh.si);
+    a.so = static_cast<int>(sh.so);
+    Scratch part(no_workspace(), a.num_chunks * sh.in * sh.so * static_cast<int64_t>(sizeof(float)), s);
+    a.part = static_cast<float*>(part.ptr);
+    a.gw = grad_weight->data;
+    launch_rgcn_bdd_wgrad(a, s);
+    check_hip(hipGetLastError(), "bdd weight gradient launch");
+  }
+  API_END();
+}
+
 int DGLMINbAccess(const DGLMIGraph* graph, const DGLMIArray* feat, const int32_t* node_map,
                   const int32_t* deg_inc_node_map, int32_t times, int32_t warm_up_times,
                   double* avg_us, void* stream) {

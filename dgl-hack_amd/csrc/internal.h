@@ -744,6 +744,76 @@ void launch_gemm(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int
                  int64_t b_cs, float* C, int64_t M, int64_t N, int64_t K, int64_t splits,
                  float* partials, hipStream_t s);
 
+// Block-diagonal ("bdd") R-GCN for many relations (kernels_rgcn_bdd.hip).
+// W (R, B, s_i, s_o) row-major.  rgcn_bdd_ok: rows up to kBddMaxWidth floats both ways
+// and in * s_o (the weight gradient's register tile over 256 lanes) <= kBddMaxWgradElems.
+constexpr int64_t kBddChunk = 64;        // positions per wave of the walk
+constexpr int64_t kBddWgradChunk = 256;  // segments per workgroup of the weight gradient
+constexpr int64_t kBddMaxWidth = 1024;
+constexpr int64_t kBddMaxWgradElems = 16384;
+bool rgcn_bdd_ok(int64_t in, int64_t out, int64_t bases);
+// One CSR (indices / eids / rows per position) regrouped stably by (row, relation):
+// cols / rel / eid per new position (indptr and rows are unchanged).  With seg_pos also
+// the relation-major list of the (row, relation) segments: segment s starts at position
+// seg_pos[s] of the regrouped walk, has seg_first[s + 1] - seg_first[s] positions and
+// row seg_row[s]; relation r's segments are rel_seg[r] .. rel_seg[r + 1], its weight
+// gradient chunks chunk_ptr[r] .. chunk_ptr[r + 1] (both R + 1 values).  O(nnz + R).
+struct BddBuild {
+  const int32_t* indices;
+  const int32_t* eids;
+  const int32_t* rows;
+  const int32_t* etypes;
+  int64_t num_rows, nnz, num_rels;
+  int32_t* cols;
+  int32_t* rel;
+  int32_t* eid;
+  int32_t* seg_pos;    // nnz, or NULL: no segment list
+  int32_t* seg_row;    // nnz
+  int32_t* seg_first;  // nnz + 1
+  int32_t* rel_seg;    // R + 1
+  int32_t* chunk_ptr;  // R + 1
+};
+hipError_t rgcn_bdd_build(const BddBuild& b, hipStream_t s);
+// out[p] = norm[eid[p]]
+void launch_rgcn_bdd_norm(const float* norm, const int32_t* eid, int64_t n, float* out, hipStream_t s);
+struct BddArgs {
+  const int32_t* indptr;  // the walk: rows own the output
+  const int32_t* rows;
+  const int32_t* cols;
+  const int32_t* rel;
+  const float* norm;      // per position, NULL = 1
+  int64_t num_rows, nnz;
+  const float* x;         // gathered table, wi floats per row
+  const float* W;
+  float* out;             // num_rows x wo
+  int64_t wi, wo;         // forward: (in, out); transposed: (out, in)
+  int nb, si, so;
+  const float* bias;      // wo, or NULL
+  const float* addend;    // num_rows x wo, or NULL
+  float* carry;           // CarryLayout(rgcn_bdd_chunks(nnz), wo)
+  int32_t* seg_cnt;
+  int64_t chunk;          // kBddChunk (fixup_role)
+};
+int64_t rgcn_bdd_chunks(int64_t nnz);
+void launch_rgcn_bdd(bool transposed, const BddArgs& a, hipStream_t s);
+struct BddWgradArgs {
+  const int32_t* seg_pos;
+  const int32_t* seg_row;
+  const int32_t* seg_first;
+  const int32_t* rel_seg;
+  const int32_t* chunk_ptr;
+  int64_t R, num_chunks;
+  const int32_t* cols;    // the forward walk's columns and norm
+  const float* norm;
+  const float* x;         // (N_src, fi)
+  const float* g;         // grad_out (N_dst, fo)
+  int64_t fi, fo;
+  int si, so;
+  float* part;            // num_chunks x fi * so
+  float* gw;              // (R, fi * so)
+};
+void launch_rgcn_bdd_wgrad(const BddWgradArgs& a, hipStream_t s);
+
 // Segment kernels (kernels_segment.hip): rows 0..num_rows-1 of an (N, F) table in
 // position order, segment b = rows offsets[b] .. offsets[b + 1] (a batch of graphs'
 // nodes or edges).  No gather, no index stream.

@@ -94,6 +94,21 @@ class RgcnState(ctypes.Structure):
     ]
 
 
+class RgcnBddState(ctypes.Structure):
+    """DGLMIRgcnBddState (include/dglmi.h): per-graph state of the bdd kernels."""
+    _fields_ = [
+        ("etypes", ctypes.c_void_p),
+        ("norm", ctypes.c_void_p),
+        ("num_rels", ctypes.c_int32),
+        ("nnz", ctypes.c_int64),
+    ] + [(name, ctypes.c_void_p) for name in (
+        "in_cols", "in_rel", "in_eid", "in_norm", "out_cols", "out_rel", "out_eid", "out_norm",
+        "seg_pos", "seg_row", "seg_first", "rel_seg", "chunk_ptr")] + [
+        ("num_chunks", ctypes.c_int64),
+        ("owner", ctypes.c_void_p),
+    ]
+
+
 class Epilogue(ctypes.Structure):
     _fields_ = [
         ("row_mul", ctypes.c_void_p),
@@ -376,6 +391,23 @@ _SIGS = {
     "DGLMIRgcnGemmInstance": (ctypes.c_int, [ctypes.c_int64] * 7 + [ctypes.c_int, ctypes.c_int,
                                                                    ctypes.c_int64]),
     "DGLMIRgcnFusedInstance": (ctypes.c_int, [ctypes.c_int64] * 5),
+    "DGLMIRgcnBddOk": (ctypes.c_int, [ctypes.c_int64] * 3),
+    "DGLMIRgcnBddChunk": (ctypes.c_int64, []),
+    "DGLMIRgcnBddWgradChunk": (ctypes.c_int64, []),
+    "DGLMIRgcnBddPrepare": (ctypes.c_int, [
+        ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.c_int32,
+        ctypes.POINTER(RgcnBddState), ctypes.c_void_p]),
+    "DGLMIRgcnBddRefreshNorm": (ctypes.c_int, [
+        ctypes.POINTER(Array), ctypes.POINTER(RgcnBddState), ctypes.c_void_p]),
+    "DGLMIRgcnBddRelease": (ctypes.c_int, [ctypes.POINTER(RgcnBddState)]),
+    "DGLMIRgcnBddForward": (ctypes.c_int, [
+        ctypes.POINTER(Graph), ctypes.POINTER(RgcnBddState), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.c_int32, ctypes.POINTER(Array), ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.POINTER(Array), ctypes.c_void_p]),
+    "DGLMIRgcnBddBackward": (ctypes.c_int, [
+        ctypes.POINTER(Graph), ctypes.POINTER(RgcnBddState), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.c_int32, ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.c_void_p]),
     "DGLMINbAccess": (ctypes.c_int, [
         ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),

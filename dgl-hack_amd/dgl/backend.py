@@ -840,6 +840,89 @@ def rgcn_fused_layer1(route, x, weight, loop_weight=None, bias=None):
                                   None if loop_weight is None else loop_weight.contiguous(), bias)
 
 
+class _RgcnBddLayer(th.autograd.Function):
+    """RelGraphConv's "bdd" layer on the segment kernels (DGLMIRgcnBddForward / Backward,
+    DESIGN.md 4.4c): aggregate every (destination, relation) segment, transform it once
+    with the relation's blocks; no (N, R, out) table.  Gradients for x (the transposed
+    walk over the (source, relation) out-CSR), the weight (over the relation-major
+    segments), the bias and the addend; the norm is constant."""
+
+    @staticmethod
+    def forward(ctx, gidx, state, norm, num_bases, x, weight, bias, addend):
+        out = x.new_empty((gidx.num_dst, weight.shape[1] // (x.shape[1] // num_bases)))
+        K.rgcn_bdd_forward(gidx, state, x, weight, num_bases, norm, out, bias=bias, addend=addend)
+        ctx.gidx, ctx.state, ctx.norm, ctx.num_bases = gidx, state, norm, num_bases
+        ctx.has_bias, ctx.has_addend = bias is not None, addend is not None
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        g = grad_out.contiguous()
+        gx = th.empty_like(x) if ctx.needs_input_grad[4] else None
+        gw = th.empty_like(weight) if ctx.needs_input_grad[5] else None
+        if gx is not None or gw is not None:
+            K.rgcn_bdd_backward(ctx.gidx, ctx.state, x, weight, ctx.num_bases, ctx.norm, g, gx, gw)
+        gb = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[6] else None
+        ga = g if ctx.has_addend and ctx.needs_input_grad[7] else None
+        return None, None, None, None, gx, gw, gb, ga
+
+
+def rgcn_bdd_route(graph, x, weight_shape, norm, etypes, force=False):
+    """(gidx, state, norm flat or None, num_bases) when a "bdd" RelGraphConv layer of
+    ``weight_shape`` = (R, in, out, B) can run on the segment kernels (kernels_rgcn_bdd.hip),
+    else None: fp32 2-D x, a 32-bit device CSR with edges, norm None or a constant fp32
+    tensor with one value per edge, in and out <= 1024 and in * s_o <= 16384.  The state
+    (``kernel.RgcnBddState``, O(E + R)) is built once per graph, device and etypes and
+    rebuilt when etypes is written in place, the previous one released first; a new or
+    rewritten norm only re-gathers its two copies.  Large graphs with few relations
+    (E >= 2^20 and R N < 2 E: the table is no larger than two values per edge) stay on
+    the table path, where forward + backward measured 12 % faster (DESIGN.md 4.4c);
+    ``force`` takes the route there too."""
+    R, fi, fo, nb = weight_shape
+    if not (isinstance(x, th.Tensor) and x.is_cuda and x.dtype == th.float32 and x.dim() == 2
+            and x.shape[1] == fi and K.rgcn_bdd_ok(fi, fo, nb)):
+        return None
+    if norm is not None and (norm.requires_grad or not norm.is_cuda or norm.dtype != th.float32
+                             or norm.numel() != graph.number_of_edges()):
+        return None
+    if etypes is None or not isinstance(etypes, th.Tensor) or etypes.device != x.device:
+        return None
+    gi = graph._graph
+    if x.shape[0] != graph.number_of_nodes() or gi.device_bits() != 32:
+        return None
+    E = graph.number_of_edges()
+    if E == 0 or etypes.numel() != E:
+        return None
+    if not force and E >= (1 << 20) and R * x.shape[0] < 2 * E:
+        return None
+    key = (str(x.device), int(R), etypes.data_ptr(), etypes._version, int(etypes.numel()))
+    hit = gi.__dict__.get("_rgcn_bdd")
+    nf = None if norm is None else _flat_norm(gi, norm)
+    if hit is None or hit[0] != key:
+        gidx = gi.get_immutable_gidx(x.device)
+        et = etypes.reshape(-1)
+        if int(et.min()) < 0 or int(et.max()) >= R:
+            raise DGLError("edge type out of range [0, %d)" % R)
+        et32 = et.to(th.int32).contiguous()
+        old = gi.__dict__.pop("_rgcn_bdd", None)
+        if old is not None:
+            old[2].release()  # before allocating the next
+        # the cache holds the caller's etypes, so its address stays theirs
+        hit = (key, gidx, K.RgcnBddState(gidx, nf, R, et32), etypes)
+        gi.__dict__["_rgcn_bdd"] = hit
+    return hit[1], hit[2], nf, int(nb)
+
+
+def rgcn_bdd_layer(route, x, weight, bias=None, addend=None):
+    """out = sum_r W_r . (per-(destination, relation) sums of norm_e x[u]) + bias + addend on
+    ``route`` (rgcn_bdd_route); weight (R, B * s_i * s_o) as RelGraphConv keeps it."""
+    gidx, state, nf, nb = route
+    return _RgcnBddLayer.apply(gidx, state, nf, nb, x.contiguous(), weight.contiguous(), bias,
+                               None if addend is None else addend.contiguous())
+
+
 def rgcn_layer0(graph, weight, norm, etypes=None):
     """Layer with one-hot (node id) input: ret[v] = sum_e W[type_e, u] * norm_e.
 

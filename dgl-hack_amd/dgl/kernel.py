@@ -1086,6 +1086,98 @@ def rgcn_layer1_backward(graph, hidden, weight, norm, grad_out, grad_hidden, gra
         _arr(grad_weight, "grad_weight"), _stream(grad_out)))
 
 
+# ---- block-diagonal ("bdd") R-GCN for many relations (kernels_rgcn_bdd.hip) -----------------
+# positions per wave of the walk and segments per workgroup of the weight gradient
+# (internal.h kBddChunk / kBddWgradChunk; RgcnBddState checks them against the library)
+RGCN_BDD_CHUNK = 64
+RGCN_BDD_WGRAD_CHUNK = 256
+
+
+def rgcn_bdd_ok(in_feat, out_feat, num_bases):
+    """DGLMIRgcnBddOk: rows up to 1024 floats both ways and in * s_o <= 16384."""
+    if num_bases < 1 or in_feat < 1 or out_feat < 1 or in_feat % num_bases or out_feat % num_bases:
+        return False
+    return in_feat <= 1024 and out_feat <= 1024 and in_feat * (out_feat // num_bases) <= 16384
+
+
+class RgcnBddState:
+    """A prepared DGLMIRgcnBddState: both CSRs of ``graph`` regrouped by (row, relation)
+    and the relation-major segment list, O(E + R) device memory.  Holds etypes (and the
+    norm its copies were gathered from).  ``sync_norm`` re-gathers the two norm copies for
+    a new or rewritten norm.  Released by ``release()`` or with the object."""
+
+    live = 0
+
+    def __init__(self, graph, norm, num_rels, etypes):
+        et = _etypes(graph, etypes)
+        lib = _ffi.lib()
+        if (lib.DGLMIRgcnBddChunk(), lib.DGLMIRgcnBddWgradChunk()) != \
+                (RGCN_BDD_CHUNK, RGCN_BDD_WGRAD_CHUNK):
+            raise DGLError("kernel.RGCN_BDD_CHUNK / RGCN_BDD_WGRAD_CHUNK differ from the library's")
+        self.etypes, self.norm, self.norm_version = et, None, None
+        self.num_rels = int(num_rels)
+        self.c = _ffi.RgcnBddState()
+        g = graph.cstruct()
+        g.etypes = et.data_ptr()
+        check_call(lib.DGLMIRgcnBddPrepare(ctypes.byref(g), None, self.num_rels,
+                                           ctypes.byref(self.c), _stream(et)))
+        import weakref
+        RgcnBddState.live += 1
+        self._fin = weakref.finalize(self, RgcnBddState._free, self.c)
+        self.sync_norm(norm)
+
+    @staticmethod
+    def _free(c):
+        _ffi.lib().DGLMIRgcnBddRelease(ctypes.byref(c))
+        RgcnBddState.live -= 1
+
+    def release(self):
+        self._fin()
+
+    def sync_norm(self, norm):
+        """Before a call with ``norm`` (flat, contiguous, or None = every edge weighs 1)."""
+        if norm is None or (self.norm is not None and norm.data_ptr() == self.norm.data_ptr()
+                            and norm._version == self.norm_version):
+            return
+        check_call(_ffi.lib().DGLMIRgcnBddRefreshNorm(_arr(norm, "norm"), ctypes.byref(self.c),
+                                                      _stream(norm)))
+        self.norm, self.norm_version = norm, norm._version
+
+
+def _rgcn_bdd_call(graph, state, norm, tensors):
+    _check_ctx(graph, tensors + [("norm", norm)])
+    if not state._fin.alive:
+        raise DGLError("the bdd state was released")
+    state.sync_norm(norm)
+    g = graph.cstruct()
+    g.etypes = state.etypes.data_ptr()
+    return g
+
+
+def rgcn_bdd_forward(graph, state, x, weight, num_bases, norm, out, bias=None, addend=None):
+    """DGLMIRgcnBddForward: out[v] = sum_r W_r . (sum_{e in (v, r)} norm_e x[u]) + bias +
+    addend[v]; weight (R, B * s_i * s_o), norm flat or None."""
+    g = _rgcn_bdd_call(graph, state, norm, [("x", x), ("weight", weight), ("out", out),
+                                            ("bias", bias), ("addend", addend)])
+    epi = _epilogue((None, None, bias, addend), out)
+    check_call(_ffi.lib().DGLMIRgcnBddForward(
+        ctypes.byref(g), ctypes.byref(state.c), _arr(x, "x"), _arr(weight, "weight"),
+        int(num_bases), _arr(norm, "norm"), None if epi is None else epi.bias,
+        None if epi is None else epi.addend, _arr(out, "out"), _stream(out)))
+
+
+def rgcn_bdd_backward(graph, state, x, weight, num_bases, norm, grad_out, grad_x=None,
+                      grad_weight=None):
+    """DGLMIRgcnBddBackward: the input gradient (the transposed walk over the (source,
+    relation) out-CSR) and / or the weight gradient (over the relation-major segments)."""
+    g = _rgcn_bdd_call(graph, state, norm, [("x", x), ("weight", weight), ("grad_out", grad_out),
+                                            ("grad_x", grad_x), ("grad_weight", grad_weight)])
+    check_call(_ffi.lib().DGLMIRgcnBddBackward(
+        ctypes.byref(g), ctypes.byref(state.c), _arr(x, "x"), _arr(weight, "weight"),
+        int(num_bases), _arr(norm, "norm"), _arr(grad_out, "grad_out"), _arr(grad_x, "grad_x"),
+        _arr(grad_weight, "grad_weight"), _stream(grad_out)))
+
+
 # ---- segment kernels (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -------------------
 class Segments:
     """The row segments of a batch for the DGLMISegment* entries: ``offsets`` a device

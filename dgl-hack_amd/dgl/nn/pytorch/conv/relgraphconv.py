@@ -9,7 +9,12 @@ on MFMA) and all relations are aggregated by one typed gather kernel
 an F_in x F_out product.  Layers whose gathered rows are 64 floats both ways
 (64 -> 64, up to 4 relations) with a constant norm instead run the hack's fused
 layer-1 C entries (aggregate per relation, then transform, in one kernel; DESIGN.md
-4.4).
+4.4).  The "bdd" regulariser (block-diagonal weights, usually with hundreds of
+relations) runs on segment kernels of its own: every (destination, relation) segment is
+aggregated and then multiplied once by that relation's blocks, forward, input gradient
+and weight gradient, without a per-(node, relation) table; layers
+outside their range (rows wider than 1024 floats, a norm that needs a gradient, 64-bit
+CSRs) keep the table + typed-gather path.
 """
 import torch as th
 from torch import nn
@@ -96,6 +101,18 @@ class RelGraphConv(nn.Module):
                 node_repr = B.rgcn_fused_layer1(route, x, self._relation_weights(),
                                                 self.loop_weight if self.self_loop else None,
                                                 self.h_bias if self.bias else None)
+                if self.activation:
+                    node_repr = self.activation(node_repr)
+                return self.dropout(node_repr)
+        if self.use_fused and self.regularizer == "bdd":
+            route = B.rgcn_bdd_route(g, x, (self.num_rels, self.in_feat, self.out_feat,
+                                            self.num_bases), norm, etypes)
+            if route is not None:
+                # aggregate per (destination, relation), then one block product per segment
+                # (B.rgcn_bdd_layer); bias and self-loop term added in its output pass
+                loop = B.project(x, self.loop_weight) if self.self_loop else None
+                node_repr = B.rgcn_bdd_layer(route, x, self.weight,
+                                             self.h_bias if self.bias else None, loop)
                 if self.activation:
                     node_repr = self.activation(node_repr)
                 return self.dropout(node_repr)

@@ -657,6 +657,65 @@ int DGLMIRgcnRefreshNorm(const DGLMIGraph* graph, const DGLMIArray* norm, DGLMIR
                          void* stream);
 int DGLMIRgcnRelease(DGLMIRgcnState* state);
 
+/* ---- RelGraphConv's block-diagonal decomposition ("bdd") for many relations ------
+ * (extension; the reference does one bmm per edge in a Python message function,
+ * relgraphconv.py:140-150).  weight (R, B s_i s_o) holds B blocks of (s_i, s_o) per
+ * relation, in = B s_i, out = B s_o:
+ *   out[v, b s_o + j] = sum_{e = (u -> v)} norm[e] sum_i x[u, b s_i + i] W[etypes[e], b, i, j]
+ * computed as sum_r W_r . (sum_{e in (v, r)} norm[e] x[u]): the edges of every
+ * (destination, relation) segment are aggregated first, then transformed once; nothing
+ * of size R x N is built.  DGLMIRgcnBddPrepare builds, on the device and once per
+ * graph and graph->etypes, both CSRs regrouped stably by (row, relation) (column,
+ * relation, edge id and norm per position) and the relation-major list of the
+ * (destination, relation) segments for the weight gradient; O(E + R) memory, the
+ * library's until DGLMIRgcnBddRelease.  `norm` (one float per edge id) may be NULL
+ * (every edge weighs 1); DGLMIRgcnBddRefreshNorm re-gathers the two norm copies from a
+ * new or rewritten norm (no sort).  The entries take norm NULL or the pointer the
+ * copies were gathered from.  No floating-point atomics: results are bit-identical
+ * from run to run.  DGLMIRgcnBddOk(in, out, bases): the shapes served (in, out <= 1024
+ * and in * s_o <= 16384, the weight gradient's register tile). */
+typedef struct DGLMIRgcnBddState {
+  const int32_t* etypes;   /* the graph->etypes pointer the state was built from */
+  const float* norm;       /* the norm pointer of the cached copies, or NULL */
+  int32_t num_rels;
+  int64_t nnz;
+  const int32_t* in_cols;  /* in-CSR regrouped by (destination, relation): source, */
+  const int32_t* in_rel;   /* relation, */
+  const int32_t* in_eid;   /* edge id */
+  float* in_norm;          /* and norm per position */
+  const int32_t* out_cols; /* out-CSR regrouped by (source, relation): destination, .. */
+  const int32_t* out_rel;
+  const int32_t* out_eid;
+  float* out_norm;
+  const int32_t* seg_pos;   /* relation-major segments: first position in the in walk, */
+  const int32_t* seg_row;   /* destination, */
+  const int32_t* seg_first; /* lengths as differences (nnz + 1 values) */
+  const int32_t* rel_seg;   /* R + 1: relation r's segments */
+  const int32_t* chunk_ptr; /* R + 1: relation r's weight-gradient chunks */
+  int64_t num_chunks;       /* chunk_ptr[R] */
+  void* owner;              /* library-private */
+} DGLMIRgcnBddState;
+int DGLMIRgcnBddOk(int64_t in_feat, int64_t out_feat, int64_t num_bases);
+/* positions per wave of the walk; segments per workgroup of the weight gradient */
+int64_t DGLMIRgcnBddChunk(void);
+int64_t DGLMIRgcnBddWgradChunk(void);
+int DGLMIRgcnBddPrepare(const DGLMIGraph* graph, const DGLMIArray* norm, int32_t num_rels,
+                        DGLMIRgcnBddState* state, void* stream);
+int DGLMIRgcnBddRefreshNorm(const DGLMIArray* norm, DGLMIRgcnBddState* state, void* stream);
+int DGLMIRgcnBddRelease(DGLMIRgcnBddState* state);
+/* out (N_dst, out) = the layer above + bias (out floats) + addend (N_dst, out), each
+ * optional.  x (N_src, in), weight (R, B s_i s_o). */
+int DGLMIRgcnBddForward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state,
+                        const DGLMIArray* x, const DGLMIArray* weight, int32_t num_bases,
+                        const DGLMIArray* norm, const float* bias, const float* addend,
+                        DGLMIArray* out, void* stream);
+/* grad_x (N_src, in) and / or grad_weight (R, B s_i s_o) from grad_out (N_dst, out);
+ * either may be NULL.  Both are overwritten. */
+int DGLMIRgcnBddBackward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state,
+                         const DGLMIArray* x, const DGLMIArray* weight, int32_t num_bases,
+                         const DGLMIArray* norm, const DGLMIArray* grad_out, DGLMIArray* grad_x,
+                         DGLMIArray* grad_weight, void* stream);
+
 /* _CAPI_DGLRgcnLayer0(G, weight, norm, ret):
  * ret[v, :] = sum_{e=(u->v)} weight[etypes[e], u, :] * norm[e];
  * weight (R, N_src, F), ret (N_dst, F). */
