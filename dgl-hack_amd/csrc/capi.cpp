@@ -2778,6 +2778,41 @@ void bdd_walk(bool transposed, const DGLMICsr& c, const int32_t* cols, const int
   launch_rgcn_bdd(transposed, a, s);
   check_hip(hipGetLastError(), "bdd walk launch");
 }
+
+// shapes of a GMM call on the CSR `c`: x (c.num_cols, width), pseudo (E, dim), mu and
+// inv_sigma (K, dim); fills the walk and the mixture of `a`
+void gmm_common(const DGLMIGraph* graph, const DGLMICsr& c, const char* which, const DGLMIArray* x,
+                const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
+                GmmArgs& a) {
+  check_graph32(graph, "GMM aggregation");
+  check_csr(c, which, true);
+  check_array(x, "x");
+  check_array(pseudo, "pseudo");
+  check_array(mu, "mu");
+  check_array(inv_sigma, "inv_sigma");
+  DGLMI_CHECK(x->ndim == 2 && pseudo->ndim == 2 && mu->ndim == 2 && inv_sigma->ndim == 2,
+              "x, pseudo, mu and inv_sigma are 2-D");
+  DGLMI_CHECK(x->shape[0] == c.num_cols, "x needs one row per column node of the walk");
+  DGLMI_CHECK(pseudo->shape[0] == c.nnz, "pseudo needs one row per edge");
+  DGLMI_CHECK(mu->shape[1] == pseudo->shape[1], "mu must be (K, dim) with pseudo's dim");
+  DGLMI_CHECK(inv_sigma->shape[0] == mu->shape[0] && inv_sigma->shape[1] == mu->shape[1],
+              "inv_sigma must have mu's shape");
+  DGLMI_CHECK(gmm_ok(x->shape[1], mu->shape[0], mu->shape[1]), "unsupported GMM shape (DGLMIGmmOk)");
+  a.indptr = c.indptr;
+  a.rows = c.rows;
+  a.cols = c.indices;
+  a.eids = c.data;
+  a.num_rows = c.num_rows;
+  a.nnz = c.nnz;
+  a.x = x->data;
+  a.width = x->shape[1];
+  a.pseudo = pseudo->data;
+  a.mu = mu->data;
+  a.inv_sigma = inv_sigma->data;
+  a.K = static_cast<int>(mu->shape[0]);
+  a.dim = static_cast<int>(mu->shape[1]);
+  a.chunk = kGmmChunk;
+}
 }  // namespace
 
 extern "C" {
@@ -2840,6 +2875,75 @@ int DGLMIRgcnBddBackward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state
     launch_rgcn_bdd_wgrad(a, s);
     check_hip(hipGetLastError(), "bdd weight gradient launch");
   }
+  API_END();
+}
+
+int DGLMIGmmOk(int64_t width, int64_t num_kernels, int64_t dim) {
+  return gmm_ok(width, num_kernels, dim) ? 1 : 0;
+}
+int64_t DGLMIGmmChunk(void) { return kGmmChunk; }
+int32_t DGLMIGmmKTile(int64_t width) { return gmm_k_tile(width); }
+
+int DGLMIGmmAggregate(const DGLMIGraph* graph, int32_t transposed, const DGLMIArray* x,
+                      const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
+                      const DGLMIArray* row_scale, DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  const DGLMICsr& c = transposed ? graph->out_csr : graph->in_csr;
+  GmmArgs a{};
+  gmm_common(graph, c, transposed ? "out_csr" : "in_csr", x, pseudo, mu, inv_sigma, a);
+  check_array(out, "out");
+  DGLMI_CHECK(out->ndim == 2 && out->shape[0] == c.num_rows && out->shape[1] == a.K * a.width,
+              "out must be (rows of the walk, K * width)");
+  if (row_scale != nullptr) {
+    check_array(row_scale, "row_scale");
+    DGLMI_CHECK(row_scale->ndim == 1 && row_scale->shape[0] == c.num_rows,
+                "row_scale needs one value per row of the walk");
+    a.row_scale = row_scale->data;
+  }
+  a.out = out->data;
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const CarryLayout lay(gmm_chunks(c.nnz), static_cast<int64_t>(a.K) * a.width);
+  Scratch ws(no_workspace(), lay.bytes, s);
+  lay.point(a, ws.ptr);
+  launch_gmm_aggregate(a, s);
+  check_hip(hipGetLastError(), "GMM aggregate launch");
+  API_END();
+}
+
+int DGLMIGmmEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* dA,
+                     const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
+                     DGLMIArray* dpseudo, DGLMIArray* dmu, DGLMIArray* dinv_sigma, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  const DGLMICsr& c = graph->in_csr;
+  GmmArgs a{};
+  gmm_common(graph, c, "in_csr", x, pseudo, mu, inv_sigma, a);
+  check_array(dA, "dA");
+  DGLMI_CHECK(dA->ndim == 2 && dA->shape[0] == c.num_rows && dA->shape[1] == a.K * a.width,
+              "dA must be (destination rows, K * width)");
+  a.dA = dA->data;
+  const DGLMIArray* like[3] = {pseudo, mu, inv_sigma};
+  DGLMIArray* outs[3] = {dpseudo, dmu, dinv_sigma};
+  const char* names[3] = {"dpseudo", "dmu", "dinv_sigma"};
+  for (int i = 0; i < 3; ++i) {
+    if (outs[i] == nullptr) continue;
+    check_array(outs[i], names[i]);
+    DGLMI_CHECK(outs[i]->ndim == 2 && outs[i]->shape[0] == like[i]->shape[0] &&
+                    outs[i]->shape[1] == like[i]->shape[1],
+                std::string(names[i]) + " must have the shape of what it is the gradient of");
+  }
+  a.dpseudo = dpseudo ? dpseudo->data : nullptr;
+  a.dmu = dmu ? dmu->data : nullptr;
+  a.dinv_sigma = dinv_sigma ? dinv_sigma->data : nullptr;
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Scratch part(no_workspace(),
+               gmm_records(c.nnz) * 2 * a.K * a.dim * static_cast<int64_t>(sizeof(float)), s);
+  a.part = static_cast<float*>(part.ptr);
+  launch_gmm_edge_grad(a, s);
+  check_hip(hipGetLastError(), "GMM edge gradient launch");
   API_END();
 }
 

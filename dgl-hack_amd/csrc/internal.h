@@ -814,6 +814,65 @@ struct BddWgradArgs {
 };
 void launch_rgcn_bdd_wgrad(const BddWgradArgs& a, hipStream_t s);
 
+// GMMConv's Gaussian-mixture aggregation (kernels_gmm.hip):
+//   out[r, k, :] = scale[r] sum_{p in row r} w_k(eid_p) x[col_p, :],
+//   w_k(e) = exp(-1/2 sum_d (pseudo[e, d] - mu[k, d])^2 inv_sigma[k, d]^2)
+// over one CSR (in-CSR: the forward; out-CSR: the input gradient), and the gradients of
+// pseudo, mu and inv_sigma over the in-CSR.  gmm_ok: the shapes served.
+constexpr int64_t kGmmChunk = 64;          // positions per wave of the walks
+constexpr int64_t kGmmMaxWidth = 512;      // 8 columns per lane
+constexpr int kGmmMaxK = 32;
+constexpr int kGmmMaxDim = 8;
+constexpr int kGmmAccBudget = 32;          // accumulators per lane: K tile x columns per lane
+constexpr int64_t kGmmMaxRecords = 4096;   // partial records of the parameter gradients
+inline bool gmm_ok(int64_t width, int64_t K, int64_t dim) {
+  return width >= 1 && width <= kGmmMaxWidth && K >= 1 && K <= kGmmMaxK && dim >= 1 &&
+         dim <= kGmmMaxDim;
+}
+// columns per lane at a width, and the kernels k_gmm_aggregate keeps in registers there
+inline int gmm_cols_per_lane(int64_t width) {
+  return width <= 64 ? 1 : width <= 128 ? 2 : width <= 256 ? 4 : 8;
+}
+inline int gmm_k_tile(int64_t width) {
+  const int t = kGmmAccBudget / gmm_cols_per_lane(width);
+  return t < kGmmMaxK ? t : kGmmMaxK;
+}
+__host__ __device__ inline int64_t gmm_chunks(int64_t nnz) { return nnz > 0 ? (nnz + kGmmChunk - 1) / kGmmChunk : 1; }
+// chunks per partial record and the record count: functions of nnz alone
+inline int64_t gmm_chunks_per_record(int64_t nnz) {
+  return (gmm_chunks(nnz) + kGmmMaxRecords - 1) / kGmmMaxRecords;
+}
+inline int64_t gmm_records(int64_t nnz) {
+  const int64_t cpr = gmm_chunks_per_record(nnz);
+  return nnz > 0 ? (gmm_chunks(nnz) + cpr - 1) / cpr : 0;
+}
+struct GmmArgs {
+  const int32_t* indptr;  // the walk: rows own the output
+  const int32_t* rows;
+  const int32_t* cols;
+  const int32_t* eids;    // edge id per position: pseudo's row
+  int64_t num_rows, nnz;
+  const float* x;         // gathered table, width floats per row
+  int64_t width;
+  const float* pseudo;    // (E, dim)
+  const float* mu;        // (K, dim)
+  const float* inv_sigma; // (K, dim)
+  int K, dim;
+  const float* row_scale; // num_rows, or NULL
+  float* out;             // num_rows x K * width
+  float* carry;           // CarryLayout(gmm_chunks(nnz), K * width)
+  int32_t* seg_cnt;
+  int64_t chunk;          // kGmmChunk (fixup_role)
+  // k_gmm_edge_grad (the in-CSR): dA (num_rows, K * width); outputs may be NULL
+  const float* dA;
+  float* dpseudo;         // (E, dim)
+  float* dmu;             // (K, dim)
+  float* dinv_sigma;      // (K, dim)
+  float* part;            // gmm_records(nnz) x 2 K dim
+};
+void launch_gmm_aggregate(const GmmArgs& a, hipStream_t s);
+void launch_gmm_edge_grad(const GmmArgs& a, hipStream_t s);
+
 // Segment kernels (kernels_segment.hip): rows 0..num_rows-1 of an (N, F) table in
 // position order, segment b = rows offsets[b] .. offsets[b + 1] (a batch of graphs'
 // nodes or edges).  No gather, no index stream.

@@ -408,6 +408,17 @@ _SIGS = {
         ctypes.POINTER(Graph), ctypes.POINTER(RgcnBddState), ctypes.POINTER(Array),
         ctypes.POINTER(Array), ctypes.c_int32, ctypes.POINTER(Array), ctypes.POINTER(Array),
         ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.c_void_p]),
+    "DGLMIGmmOk": (ctypes.c_int, [ctypes.c_int64] * 3),
+    "DGLMIGmmChunk": (ctypes.c_int64, []),
+    "DGLMIGmmKTile": (ctypes.c_int32, [ctypes.c_int64]),
+    "DGLMIGmmAggregate": (ctypes.c_int, [
+        ctypes.POINTER(Graph), ctypes.c_int32, ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.c_void_p]),
+    "DGLMIGmmEdgeGrad": (ctypes.c_int, [
+        ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array), ctypes.POINTER(Array),
+        ctypes.POINTER(Array), ctypes.c_void_p]),
     "DGLMINbAccess": (ctypes.c_int, [
         ctypes.POINTER(Graph), ctypes.POINTER(Array), ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]),

@@ -923,6 +923,81 @@ def rgcn_bdd_layer(route, x, weight, bias=None, addend=None):
                                None if addend is None else addend.contiguous())
 
 
+class _GmmAggregate(th.autograd.Function):
+    """GMMConv on the aggregate-first kernels (kernels_gmm.hip):
+    A[v, k, :] = scale[v] sum_e w_k(e) x[u, :] (one k_gmm_aggregate launch on the in-CSR),
+    then out = A.view(N, K in) @ fc.view(K, out, in)^T as one GEMM.  The Function owns the
+    projection so that the input gradient is the same walk transposed over grad_out's
+    `out` floats per edge (B[u, k, :] = sum_e w_k(e) scale[v] grad_out[v, :], dx = B @ fc)
+    instead of a gather of K in-wide dA rows; A is saved for the fc gradient.  The
+    weights are recomputed by k_gmm_edge_grad for pseudo, mu and inv_sigma, never saved.
+    Gradients that needs_input_grad does not ask for are not computed."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, pseudo, mu, inv_sigma, weight, row_scale):
+        n_k, fi = mu.shape[0], x.shape[1]
+        fo = weight.shape[0] // n_k
+        A = x.new_empty((gidx.num_dst, n_k * fi))
+        K.gmm_aggregate(gidx, x, pseudo, mu, inv_sigma, A, row_scale=row_scale)
+        # fc.weight is (K out, in): row k out + o; A's columns are k in + i
+        w2 = weight.view(n_k, fo, fi).permute(0, 2, 1).reshape(n_k * fi, fo)
+        ctx.gidx, ctx.dims = gidx, (n_k, fi, fo)
+        ctx.save_for_backward(x, pseudo, mu, inv_sigma, weight, row_scale, A)
+        return A @ w2
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, pseudo, mu, inv_sigma, weight, row_scale, A = ctx.saved_tensors
+        n_k, fi, fo = ctx.dims
+        need = ctx.needs_input_grad
+        go = grad_out.contiguous()
+        gx = gp = gm = gs = gw = None
+        if need[5]:
+            gw = (A.t() @ go).view(n_k, fi, fo).permute(0, 2, 1).reshape(n_k * fo, fi)
+        gsc = go if row_scale is None else go * row_scale.view(-1, 1)
+        if need[1]:
+            Bm = go.new_empty((ctx.gidx.num_src, n_k * fo))
+            K.gmm_aggregate(ctx.gidx, gsc, pseudo, mu, inv_sigma, Bm, transposed=True)
+            gx = Bm @ weight
+        if need[2] or need[3] or need[4]:
+            dA = gsc @ weight.view(n_k, fo, fi).permute(0, 2, 1).reshape(n_k * fi, fo).t()
+            gp = th.empty_like(pseudo) if need[2] else None
+            gm = th.empty_like(mu) if need[3] else None
+            gs = th.empty_like(inv_sigma) if need[4] else None
+            K.gmm_edge_grad(ctx.gidx, x, dA, pseudo, mu, inv_sigma, gp, gm, gs)
+        return None, gx, gp, gm, gs, gw, None
+
+
+def gmm_route(graph, x, pseudo, num_kernels, dim, out_feats):
+    """The device index when GMMConv's fused form can run: fp32 2-D device features, one
+    (E, dim) fp32 pseudo row per edge id, shapes DGLMIGmmOk serves at BOTH widths (the
+    forward walks rows of x.shape[1] floats, the input gradient rows of out_feats), and
+    32-bit CSRs whose edge ids are a permutation of the positions; else None."""
+    if not (isinstance(x, th.Tensor) and x.is_cuda and x.dtype == th.float32 and x.dim() == 2
+            and isinstance(pseudo, th.Tensor) and pseudo.device == x.device
+            and pseudo.dtype == th.float32
+            and K.gmm_ok(max(x.shape[1], out_feats), num_kernels, dim)):
+        return None
+    if pseudo.numel() != graph.number_of_edges() * dim:
+        return None
+    gidx = graph._graph.get_immutable_gidx(x.device)
+    if gidx.num_bits != 32 or not gidx.eid_perm or x.shape[0] != gidx.num_src:
+        return None
+    return gidx
+
+
+def gmm_aggregate(graph_index, x, pseudo, mu, inv_sigma, weight, row_scale=None):
+    """out[v, :] = sum_k (row_scale[v] sum_{e = (u -> v)} w_k(e) x[u, :]) @ weight.view(K, out,
+    in)[k]^T with w_k(e) = exp(-1/2 sum_d (pseudo[e, d] - mu[k, d])^2 inv_sigma[k, d]^2):
+    GMMConv's sum (row_scale None) or mean (1 / in-degree, 0 where it is 0) aggregation of
+    fc(x) without the (N, K, out) projection or the (E, K) weights.  ``weight`` is
+    GMMConv.fc.weight, (K * out, in).  Differentiable in x, pseudo, mu, inv_sigma, weight."""
+    dim = mu.shape[1]
+    return _GmmAggregate.apply(graph_index, x.contiguous(), pseudo.reshape(-1, dim).contiguous(),
+                               mu.contiguous(), inv_sigma.contiguous(), weight.contiguous(),
+                               None if row_scale is None else row_scale.contiguous())
+
+
 def rgcn_layer0(graph, weight, norm, etypes=None):
     """Layer with one-hot (node id) input: ret[v] = sum_e W[type_e, u] * norm_e.
 

@@ -1178,6 +1178,56 @@ def rgcn_bdd_backward(graph, state, x, weight, num_bases, norm, grad_out, grad_x
         _arr(grad_weight, "grad_weight"), _stream(grad_out)))
 
 
+# ---- GMMConv's Gaussian-mixture aggregation (kernels_gmm.hip) --------------------------------
+# positions per wave of the walks (internal.h kGmmChunk; checked against the library)
+GMM_CHUNK = 64
+
+
+def gmm_ok(width, num_kernels, dim):
+    """DGLMIGmmOk: the shapes the GMM kernels serve (rows up to 512 floats, up to 32 kernels,
+    up to 8 pseudo-coordinates), asked of the library."""
+    return bool(_ffi.lib().DGLMIGmmOk(int(width), int(num_kernels), int(dim)))
+
+
+def gmm_k_tile(width):
+    """DGLMIGmmKTile: kernels one launch row of k_gmm_aggregate keeps in registers at this
+    width; more kernels are walked as further tiles."""
+    return int(_ffi.lib().DGLMIGmmKTile(int(width)))
+
+
+def _gmm_call(graph, tensors):
+    _check_ctx(graph, tensors)
+    if _ffi.lib().DGLMIGmmChunk() != GMM_CHUNK:
+        raise DGLError("kernel.GMM_CHUNK differs from the library's")
+    if not graph.eid_perm:
+        raise DGLError("the GMM kernels index pseudo by edge id: the graph's edge ids must be "
+                       "a permutation of its positions")
+    return graph.cstruct()
+
+
+def gmm_aggregate(graph, x, pseudo, mu, inv_sigma, out, row_scale=None, transposed=False):
+    """DGLMIGmmAggregate: out[r, k, :] = row_scale[r] sum_{e in row r} w_k(e) x[col(e), :] over
+    the in-CSR, or the out-CSR when ``transposed``; out (rows, K * width), pseudo by edge id."""
+    g = _gmm_call(graph, [("x", x), ("pseudo", pseudo), ("mu", mu), ("inv_sigma", inv_sigma),
+                          ("out", out), ("row_scale", row_scale)])
+    check_call(_ffi.lib().DGLMIGmmAggregate(
+        ctypes.byref(g), 1 if transposed else 0, _arr(x, "x"), _arr(pseudo, "pseudo"),
+        _arr(mu, "mu"), _arr(inv_sigma, "inv_sigma"), _arr(row_scale, "row_scale"),
+        _arr(out, "out"), _stream(out)))
+
+
+def gmm_edge_grad(graph, x, dA, pseudo, mu, inv_sigma, dpseudo=None, dmu=None, dinv_sigma=None):
+    """DGLMIGmmEdgeGrad: the gradients of pseudo, mu and inv_sigma (each optional) from dA
+    (N_dst, K * width), the gradient of gmm_aggregate's output with its row scale applied."""
+    g = _gmm_call(graph, [("x", x), ("dA", dA), ("pseudo", pseudo), ("mu", mu),
+                          ("inv_sigma", inv_sigma), ("dpseudo", dpseudo), ("dmu", dmu),
+                          ("dinv_sigma", dinv_sigma)])
+    check_call(_ffi.lib().DGLMIGmmEdgeGrad(
+        ctypes.byref(g), _arr(x, "x"), _arr(dA, "dA"), _arr(pseudo, "pseudo"), _arr(mu, "mu"),
+        _arr(inv_sigma, "inv_sigma"), _arr(dpseudo, "dpseudo"), _arr(dmu, "dmu"),
+        _arr(dinv_sigma, "dinv_sigma"), _stream(dA)))
+
+
 # ---- segment kernels (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -------------------
 class Segments:
     """The row segments of a batch for the DGLMISegment* entries: ``offsets`` a device

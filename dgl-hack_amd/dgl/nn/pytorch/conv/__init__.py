@@ -12,4 +12,5 @@ from .chebconv import ChebConv  # noqa: F401
 from .agnnconv import AGNNConv  # noqa: F401
 from .edgeconv import EdgeConv  # noqa: F401
 from .gatedgraphconv import GatedGraphConv  # noqa: F401
+from .gmmconv import GMMConv  # noqa: F401
 from .dense import DenseGraphConv, DenseSAGEConv, DenseChebConv  # noqa: F401

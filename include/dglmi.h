@@ -716,6 +716,38 @@ int DGLMIRgcnBddBackward(const DGLMIGraph* graph, const DGLMIRgcnBddState* state
                          const DGLMIArray* norm, const DGLMIArray* grad_out, DGLMIArray* grad_x,
                          DGLMIArray* grad_weight, void* stream);
 
+/* ---- GMMConv (MoNet): Gaussian-mixture aggregation (extension; the reference projects
+ * every source row to K * out floats and gathers that per edge, gmmconv.py:113-124).
+ * sum and mean are linear, so the edges are aggregated first and projected once:
+ *   out[r, k, :] = row_scale[r] sum_{e in row r} w_k(e) x[col(e), :]
+ *   w_k(e) = exp(-1/2 sum_d (pseudo[e, d] - mu[k, d])^2 inv_sigma[k, d]^2)
+ * over the in-CSR (transposed == 0: rows = destinations, x one row per source) or the
+ * out-CSR (transposed != 0: rows = sources, x one row per destination -- the input
+ * gradient with x = grad_out).  pseudo (E, dim) is indexed by edge id; mu and inv_sigma
+ * are (K, dim); row_scale (one float per row) may be NULL; out is (rows, K * width) and
+ * is overwritten, rows without edges with zeros.  The (E, K) weights are never stored:
+ * DGLMIGmmEdgeGrad recomputes them with the same operations.  fp32, 32-bit graphs, no
+ * floating-point atomics: bit-identical from run to run.
+ * DGLMIGmmOk(width, K, dim): the shapes served (width <= 512, K <= 32, dim <= 8).
+ * DGLMIGmmChunk(): CSR positions per wave of the walks.  DGLMIGmmKTile(width): the
+ * kernels one launch row keeps in registers at that width; more are walked as tiles. */
+int DGLMIGmmOk(int64_t width, int64_t num_kernels, int64_t dim);
+int64_t DGLMIGmmChunk(void);
+int32_t DGLMIGmmKTile(int64_t width);
+int DGLMIGmmAggregate(const DGLMIGraph* graph, int32_t transposed, const DGLMIArray* x,
+                      const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
+                      const DGLMIArray* row_scale, DGLMIArray* out, void* stream);
+/* Gradients of the mixture over the in-CSR from dA (N_dst, K * width), the gradient of
+ * DGLMIGmmAggregate's (untransposed) output with the row scale already applied:
+ *   dw_k(e) = <x[src(e)], dA[dst(e), k, :]>,  dg_k = dw_k w_k,  t = pseudo[e, d] - mu[k, d]
+ *   dpseudo[e, d] = -sum_k dg_k t inv_sigma[k, d]^2          (E, dim), every edge id once
+ *   dmu[k, d] = sum_e dg_k t inv_sigma[k, d]^2               (K, dim)
+ *   dinv_sigma[k, d] = -sum_e dg_k t^2 inv_sigma[k, d]       (K, dim)
+ * Any output may be NULL; the others are overwritten. */
+int DGLMIGmmEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* dA,
+                     const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
+                     DGLMIArray* dpseudo, DGLMIArray* dmu, DGLMIArray* dinv_sigma, void* stream);
+
 /* _CAPI_DGLRgcnLayer0(G, weight, norm, ret):
  * ret[v, :] = sum_{e=(u->v)} weight[etypes[e], u, :] * norm[e];
  * weight (R, N_src, F), ret (N_dst, F). */
