@@ -2779,6 +2779,38 @@ void bdd_walk(bool transposed, const DGLMICsr& c, const int32_t* cols, const int
   check_hip(hipGetLastError(), "bdd walk launch");
 }
 
+// the walk over `c`, the widths and what both NNConv calls share: w (E, in * out) by edge id
+// (NULL where the call does not read it), row_scale one float per destination or NULL
+void nnconv_common(const DGLMIGraph* graph, const DGLMICsr& c, const char* which, int64_t fin,
+                   int64_t fout, const DGLMIArray* w, const DGLMIArray* row_scale, int64_t num_dst,
+                   NnconvArgs& a) {
+  check_graph32(graph, "NNConv aggregation");
+  check_csr(c, which, true);
+  DGLMI_CHECK(nnconv_ok(fin, fout), "unsupported NNConv widths (DGLMINnconvOk)");
+  if (w != nullptr) {
+    check_array(w, "w");
+    DGLMI_CHECK(w->ndim == 2 && w->shape[0] == c.nnz && w->shape[1] == fin * fout,
+                "w must be (edges, in * out)");
+    a.w = w->data;
+  }
+  if (row_scale != nullptr) {
+    check_array(row_scale, "row_scale");
+    DGLMI_CHECK(row_scale->ndim == 1 && row_scale->shape[0] == num_dst,
+                "row_scale needs one value per destination node");
+    a.row_scale = row_scale->data;
+  }
+  a.indptr = c.indptr;
+  a.rows = c.rows;
+  a.cols = c.indices;
+  a.eids = c.data;
+  a.num_rows = c.num_rows;
+  a.nnz = c.nnz;
+  a.fin = static_cast<int>(fin);
+  a.fout = static_cast<int>(fout);
+  a.chunk = nnconv_chunk(fin, fout, c.nnz);
+  a.vec = nnconv_row_lanes(fout) != 0;
+}
+
 // shapes of a GMM call on the CSR `c`: x (c.num_cols, width), pseudo (E, dim), mu and
 // inv_sigma (K, dim); fills the walk and the mixture of `a`
 void gmm_common(const DGLMIGraph* graph, const DGLMICsr& c, const char* which, const DGLMIArray* x,
@@ -2944,6 +2976,80 @@ int DGLMIGmmEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIAr
   a.part = static_cast<float*>(part.ptr);
   launch_gmm_edge_grad(a, s);
   check_hip(hipGetLastError(), "GMM edge gradient launch");
+  API_END();
+}
+
+int DGLMINnconvOk(int64_t in_feats, int64_t out_feats) { return nnconv_ok(in_feats, out_feats) ? 1 : 0; }
+int64_t DGLMINnconvChunk(int64_t in_feats, int64_t out_feats, int64_t nnz) {
+  return nnconv_ok(in_feats, out_feats) && nnz >= 0 ? nnconv_chunk(in_feats, out_feats, nnz) : 0;
+}
+
+int DGLMINnconvAggregate(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* w,
+                         const DGLMIArray* row_scale, DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  const DGLMICsr& c = graph->in_csr;
+  NnconvArgs a{};
+  check_array(x, "x");
+  check_array(out, "out");
+  DGLMI_CHECK(x->ndim == 2 && out->ndim == 2, "x and out are 2-D");
+  nnconv_common(graph, c, "in_csr", x->shape[1], out->shape[1], w, row_scale, c.num_rows, a);
+  DGLMI_CHECK(x->shape[0] == c.num_cols, "x needs one row per source node");
+  DGLMI_CHECK(out->shape[0] == c.num_rows, "out needs one row per destination node");
+  a.x = x->data;
+  a.out = out->data;
+  a.rec = a.fout;
+  a.vec = a.vec && aligned16(a.w);
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const CarryLayout lay(nnconv_chunks(c.nnz, a.chunk), a.rec);
+  Scratch ws(no_workspace(), lay.bytes, s);
+  lay.point(a, ws.ptr);
+  launch_nnconv_aggregate(a, s);
+  check_hip(hipGetLastError(), "NNConv aggregate launch");
+  API_END();
+}
+
+int DGLMINnconvBackward(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* w,
+                        const DGLMIArray* g, const DGLMIArray* row_scale, DGLMIArray* dx,
+                        DGLMIArray* dw, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  const DGLMICsr& c = graph->out_csr;
+  DGLMI_CHECK(dx != nullptr || dw != nullptr, "dx and dw are both NULL");
+  const DGLMIArray* xs = dx != nullptr ? dx : x;  // (N_src, in)
+  check_array(xs, "x");
+  check_array(g, "g");
+  DGLMI_CHECK(xs->ndim == 2 && g->ndim == 2, "x, dx and g are 2-D");
+  NnconvArgs a{};
+  nnconv_common(graph, c, "out_csr", xs->shape[1], g->shape[1], dx != nullptr ? w : nullptr,
+                row_scale, c.num_cols, a);
+  DGLMI_CHECK(g->shape[0] == c.num_cols, "g needs one row per destination node");
+  a.g = g->data;
+  for (const DGLMIArray* t : {dw != nullptr ? x : nullptr, static_cast<const DGLMIArray*>(dx)}) {
+    if (t == nullptr) continue;
+    check_array(t, "x / dx");
+    DGLMI_CHECK(t->ndim == 2 && t->shape[0] == c.num_rows && t->shape[1] == a.fin,
+                "x and dx must be (source nodes, in)");
+  }
+  if (dw != nullptr) {
+    check_array(dw, "dw");
+    DGLMI_CHECK(dw->ndim == 2 && dw->shape[0] == c.nnz &&
+                    dw->shape[1] == static_cast<int64_t>(a.fin) * a.fout,
+                "dw must be (edges, in * out)");
+    a.x = x->data;
+    a.dw = dw->data;
+  }
+  a.out = dx != nullptr ? dx->data : nullptr;
+  a.rec = a.fin;
+  a.vec = a.vec && aligned16(a.w) && aligned16(a.dw);
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const CarryLayout lay(nnconv_chunks(c.nnz, a.chunk), a.rec);
+  Scratch ws(no_workspace(), dx != nullptr ? lay.bytes : 0, s);
+  if (dx != nullptr) lay.point(a, ws.ptr);
+  launch_nnconv_backward(a, s);
+  check_hip(hipGetLastError(), "NNConv backward launch");
   API_END();
 }
 

@@ -253,6 +253,26 @@ __device__ __forceinline__ void seg_fold(const FixupRole& w, int32_t* seg_cnt, i
   }
 }
 
+// The fixup of a walk whose carry records are `rec` plain float sums (k_gmm_fixup,
+// k_nnconv_fixup): the wave of `chunk` folds a cut row's carries into its head in chunk
+// order (lane k owns floats k, k + 64, ..), then the row scale where the row is finished.
+// `a`: the walk's arguments (rows, nnz, chunk, seg_cnt, out, carry, row_scale).
+template <typename Args, typename IP>
+__device__ __forceinline__ void fixup_float_records(const Args& a, IP indptr, int64_t chunk,
+                                                    int64_t rec, int lane) {
+  const FixupRole w = fixup_role(a, indptr, chunk);
+  if (!w.work) return;
+  seg_fold(w, a.seg_cnt, 64, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
+    float* dst = head ? a.out + w.r * rec : a.carry + c0 * rec;
+    const float scale = head && a.row_scale ? a.row_scale[w.r] : 1.0f;
+    for (int64_t k = lane; k < rec; k += 64) {
+      float acc = dst[k];
+      for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) acc += a.carry[c * rec + k];
+      dst[k] = acc * scale;
+    }
+  });
+}
+
 // Host side: where a chunked walk's carries and counters lie in its workspace.
 // `chunks` records of `rec_floats` floats, rounded up to 16 B, then one int32
 // counter per chunk; point() sets a.carry / a.seg_cnt for a workspace at `base`.
@@ -872,6 +892,57 @@ struct GmmArgs {
 };
 void launch_gmm_aggregate(const GmmArgs& a, hipStream_t s);
 void launch_gmm_edge_grad(const GmmArgs& a, hipStream_t s);
+
+// NNConv's per-edge weight-matrix aggregation (kernels_nnconv.hip):
+//   out[r, :] = scale[r] sum_{p in row r} x[col_p, :] . W[eid_p]       W (E, in, out)
+// over the in-CSR, and over the out-CSR dx[u, i] = sum_p <W[eid_p, i, :], scale[v] g[v, :]>
+// and dW[eid_p] = x[u] (x) scale[v] g[v].  nnconv_ok: the widths served.
+constexpr int64_t kNnMaxWidth = 256;
+constexpr int kNnAccTile = 32;                    // dx accumulators per lane (kGmmAccBudget's figure)
+constexpr int64_t kNnChunkBytes = 64 << 10;       // W bytes one wave streams, at most
+constexpr int64_t kNnMinChunkBytes = 4 << 10;     // below this a chunk is not cut further
+constexpr int64_t kNnMinChunks = 4096;            // 4 waves for each of 1024 SIMDs
+inline bool nnconv_ok(int64_t fin, int64_t fout) {
+  return fin >= 1 && fin <= kNnMaxWidth && fout >= 1 && fout <= kNnMaxWidth;
+}
+// lanes per row of W[e] in the vector instance (16 bytes each), 0: the scalar instance
+inline int nnconv_row_lanes(int64_t fout) {
+  const int64_t lr = fout / 4;
+  return fout % 4 == 0 && lr >= 1 && lr <= 64 && (lr & (lr - 1)) == 0 ? static_cast<int>(lr) : 0;
+}
+// positions per wave: a power of two from 1 to 64 (DESIGN.md 4.7c has the rule's reasons)
+__host__ __device__ inline int64_t nnconv_chunk(int64_t fin, int64_t fout, int64_t nnz) {
+  const int64_t pos = fin * fout * static_cast<int64_t>(sizeof(float));
+  int64_t ch = 64;
+  while (ch > 1 && ch * pos > kNnChunkBytes) ch >>= 1;
+  while (ch > 1 && ch * pos > kNnMinChunkBytes && (nnz + ch - 1) / ch < kNnMinChunks) ch >>= 1;
+  return ch;
+}
+__host__ __device__ inline int64_t nnconv_chunks(int64_t nnz, int64_t ch) {
+  return nnz > 0 ? (nnz + ch - 1) / ch : 1;
+}
+struct NnconvArgs {
+  const int32_t* indptr;  // the walk: rows own the reduced output (out, or dx)
+  const int32_t* rows;
+  const int32_t* cols;
+  const int32_t* eids;    // edge id per position: W's and dW's matrix
+  int64_t num_rows, nnz;
+  int fin, fout;
+  const float* x;         // (sources, in)
+  const float* w;         // (E, in * out)
+  const float* row_scale; // one per destination, or NULL
+  float* out;             // what the walk reduces: (rows, rec)
+  int64_t rec;            // floats per row of out and per carry record: out (forward), in (dx)
+  float* carry;           // CarryLayout(nnconv_chunks(nnz, chunk), rec)
+  int32_t* seg_cnt;
+  int64_t chunk;          // positions per wave (fixup_role)
+  bool vec;               // the vector instance: nnconv_row_lanes(out) != 0, w and dw 16-byte aligned
+  // backward (the out-CSR; out = dx or NULL)
+  const float* g;         // (destinations, out)
+  float* dw;              // (E, in * out), or NULL
+};
+void launch_nnconv_aggregate(const NnconvArgs& a, hipStream_t s);
+void launch_nnconv_backward(const NnconvArgs& a, hipStream_t s);
 
 // Segment kernels (kernels_segment.hip): rows 0..num_rows-1 of an (N, F) table in
 // position order, segment b = rows offsets[b] .. offsets[b + 1] (a batch of graphs'

@@ -189,20 +189,8 @@ __global__ void __launch_bounds__(kBlock) k_gmm_aggregate(GmmArgs a) {
 
 // folds a cut row's carries into its head in chunk order, then the row scale
 __global__ void __launch_bounds__(kBlock) k_gmm_fixup(GmmArgs a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const FixupRole w =
-      fixup_role(a, a.indptr, (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave);
-  if (!w.work) return;
-  const int64_t rec = (int64_t)a.K * a.width;
-  seg_fold(w, a.seg_cnt, kWave, lane, [&](bool head, int64_t c0, int64_t c1, int64_t step) {
-    float* dst = head ? a.out + w.r * rec : a.carry + c0 * rec;
-    const float scale = head && a.row_scale ? a.row_scale[w.r] : 1.0f;
-    for (int64_t k = lane; k < rec; k += kWave) {
-      float acc = dst[k];
-      for (int64_t c = head ? c0 : c0 + 1; c <= c1; c += step) acc += a.carry[c * rec + k];
-      dst[k] = acc * scale;
-    }
-  });
+  fixup_float_records(a, a.indptr, (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave,
+                      (int64_t)a.K * a.width, threadIdx.x & (kWave - 1));
 }
 
 // v[N] per lane -> the wave's sum of v[lane >> (6 - log2 N)] in every lane (a butterfly

@@ -998,6 +998,55 @@ def gmm_aggregate(graph_index, x, pseudo, mu, inv_sigma, weight, row_scale=None)
                                None if row_scale is None else row_scale.contiguous())
 
 
+class _NnconvAggregate(th.autograd.Function):
+    """NNConv on kernels_nnconv.hip: out[v] = scale[v] sum_e x[u] @ w[e], one
+    k_nnconv_aggregate launch on the in-CSR; backward one k_nnconv_backward walk over the
+    out-CSR for dx and dw together.  Saves x, w and the row scale: nothing else of size
+    E in out.  Gradients that needs_input_grad does not ask for are not computed."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, w, row_scale):
+        out = x.new_empty((gidx.num_dst, w.shape[1] // x.shape[1]))
+        K.nnconv_aggregate(gidx, x, w, out, row_scale=row_scale)
+        ctx.gidx = gidx
+        ctx.save_for_backward(x, w, row_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, w, row_scale = ctx.saved_tensors
+        dx = th.empty_like(x) if ctx.needs_input_grad[1] else None
+        dw = th.empty_like(w) if ctx.needs_input_grad[2] else None
+        if dx is not None or dw is not None:
+            K.nnconv_backward(ctx.gidx, x, w, grad_out.contiguous(), row_scale, dx=dx, dw=dw)
+        return None, dx, dw, None
+
+
+def nnconv_route(graph, x, w, in_feats, out_feats):
+    """The device index when NNConv's fused form can run: fp32 2-D device features of in_feats
+    columns, fp32 weights of in_feats * out_feats values per edge id on the same device,
+    widths DGLMINnconvOk serves, and 32-bit CSRs whose edge ids are a permutation of the
+    positions; else None."""
+    if not (isinstance(x, th.Tensor) and x.is_cuda and x.dtype == th.float32 and x.dim() == 2
+            and x.shape[1] == in_feats and isinstance(w, th.Tensor) and w.device == x.device
+            and w.dtype == th.float32 and K.nnconv_ok(in_feats, out_feats)):
+        return None
+    if w.numel() != graph.number_of_edges() * in_feats * out_feats:
+        return None
+    gidx = graph._graph.get_immutable_gidx(x.device)
+    if gidx.num_bits != 32 or not gidx.eid_perm or x.shape[0] != gidx.num_src:
+        return None
+    return gidx
+
+
+def nnconv_aggregate(graph_index, x, w, row_scale=None):
+    """out[v, :] = row_scale[v] sum_{e = (u -> v)} x[u, :] @ w[e]: NNConv's sum (row_scale None)
+    or mean (1 / in-degree, 0 where it is 0) aggregation without the (N, in, out) table.
+    ``w`` is (E, in * out), one row per edge id.  Differentiable in x and w."""
+    return _NnconvAggregate.apply(graph_index, x.contiguous(), w.contiguous(),
+                                  None if row_scale is None else row_scale.contiguous())
+
+
 def rgcn_layer0(graph, weight, norm, etypes=None):
     """Layer with one-hot (node id) input: ret[v] = sum_e W[type_e, u] * norm_e.
 

@@ -1228,6 +1228,46 @@ def gmm_edge_grad(graph, x, dA, pseudo, mu, inv_sigma, dpseudo=None, dmu=None, d
         _arr(dinv_sigma, "dinv_sigma"), _stream(dA)))
 
 
+# ---- NNConv's per-edge weight-matrix aggregation (kernels_nnconv.hip) ---------------------------
+def nnconv_ok(in_feats, out_feats):
+    """DGLMINnconvOk: the widths the NNConv kernels serve (1 to 256 each), asked of the library."""
+    return bool(_ffi.lib().DGLMINnconvOk(int(in_feats), int(out_feats)))
+
+
+def nnconv_chunk(in_feats, out_feats, nnz):
+    """DGLMINnconvChunk: CSR positions per wave of the NNConv walks at these widths and this
+    many edges (a power of two from 1 to 64)."""
+    return int(_ffi.lib().DGLMINnconvChunk(int(in_feats), int(out_feats), int(nnz)))
+
+
+def _nnconv_call(graph, tensors):
+    _check_ctx(graph, tensors)
+    if not graph.eid_perm:
+        raise DGLError("the NNConv kernels index the weight matrices by edge id: the graph's "
+                       "edge ids must be a permutation of its positions")
+    return graph.cstruct()
+
+
+def nnconv_aggregate(graph, x, w, out, row_scale=None):
+    """DGLMINnconvAggregate: out[v, :] = row_scale[v] sum_{e = (u -> v)} x[u, :] @ w[e] over the
+    in-CSR; x (N_src, in), w (E, in * out) by edge id, out (N_dst, out)."""
+    g = _nnconv_call(graph, [("x", x), ("w", w), ("out", out), ("row_scale", row_scale)])
+    check_call(_ffi.lib().DGLMINnconvAggregate(
+        ctypes.byref(g), _arr(x, "x"), _arr(w, "w"), _arr(row_scale, "row_scale"),
+        _arr(out, "out"), _stream(out)))
+
+
+def nnconv_backward(graph, x, w, g, row_scale, dx=None, dw=None):
+    """DGLMINnconvBackward: from g (N_dst, out), dx[u] = sum_e w[e] @ (row_scale[v] g[v]) and
+    dw[e] = x[u] (outer) row_scale[v] g[v], each optional, in one walk over the out-CSR.
+    Without dx, w is not read (None is fine); without dw, x is not."""
+    gr = _nnconv_call(graph, [("x", x), ("w", w), ("g", g), ("row_scale", row_scale),
+                              ("dx", dx), ("dw", dw)])
+    check_call(_ffi.lib().DGLMINnconvBackward(
+        ctypes.byref(gr), _arr(x, "x"), _arr(w, "w"), _arr(g, "g"), _arr(row_scale, "row_scale"),
+        _arr(dx, "dx"), _arr(dw, "dw"), _stream(g)))
+
+
 # ---- segment kernels (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -------------------
 class Segments:
     """The row segments of a batch for the DGLMISegment* entries: ``offsets`` a device

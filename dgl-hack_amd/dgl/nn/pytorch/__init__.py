@@ -1,7 +1,7 @@
 """PyTorch modules (``dgl.nn.pytorch``)."""
 from .conv import (GraphConv, GATConv, FusedGATConv, RelGraphConv, SAGEConv,  # noqa: F401
                    GINConv, SGConv, APPNPConv, TAGConv, ChebConv, AGNNConv, EdgeConv,
-                   GatedGraphConv, GMMConv, DenseGraphConv,
+                   GatedGraphConv, GMMConv, NNConv, DenseGraphConv,
                    DenseSAGEConv, DenseChebConv)
 from .softmax import edge_softmax  # noqa: F401
 from .glob import (SumPooling, AvgPooling, MaxPooling, SortPooling,  # noqa: F401

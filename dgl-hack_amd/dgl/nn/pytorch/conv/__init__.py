@@ -13,4 +13,5 @@ from .agnnconv import AGNNConv  # noqa: F401
 from .edgeconv import EdgeConv  # noqa: F401
 from .gatedgraphconv import GatedGraphConv  # noqa: F401
 from .gmmconv import GMMConv  # noqa: F401
+from .nnconv import NNConv  # noqa: F401
 from .dense import DenseGraphConv, DenseSAGEConv, DenseChebConv  # noqa: F401

@@ -748,6 +748,30 @@ int DGLMIGmmEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIAr
                      const DGLMIArray* pseudo, const DGLMIArray* mu, const DGLMIArray* inv_sigma,
                      DGLMIArray* dpseudo, DGLMIArray* dmu, DGLMIArray* dinv_sigma, void* stream);
 
+/* ---- NNConv (MPNN): per-edge weight-matrix aggregation (extension; the reference
+ * multiplies (N, in, 1) by (E, in, out), reduces to (N, in, out) and sums over `in`,
+ * nnconv.py:105-121).  sum and mean are linear, so the sum over `in` is taken in the walk:
+ *   out[v, :] = row_scale[v] sum_{e = (u -> v)} x[u, :] . W[e]
+ * x (N_src, in), w (E, in * out) indexed by edge id, row_scale (N_dst) or NULL, out
+ * (N_dst, out), overwritten, rows without in-edges with zeros.  fp32, 32-bit graphs, no
+ * floating-point atomics: bit-identical from run to run.
+ * DGLMINnconvOk(in, out): the widths served (1 .. 256 each).
+ * DGLMINnconvChunk(in, out, nnz): CSR positions per wave of both walks for such a call, a
+ * power of two from 1 to 64 (one position is in * out * 4 bytes of W). */
+int DGLMINnconvOk(int64_t in_feats, int64_t out_feats);
+int64_t DGLMINnconvChunk(int64_t in_feats, int64_t out_feats, int64_t nnz);
+int DGLMINnconvAggregate(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* w,
+                         const DGLMIArray* row_scale, DGLMIArray* out, void* stream);
+/* The gradients from g (N_dst, out), the gradient of DGLMINnconvAggregate's output, in one
+ * walk over the out-CSR:
+ *   dx[u, i] = sum_{e = (u -> v)} sum_o W[e, i, o] row_scale[v] g[v, o]      (N_src, in)
+ *   dw[e, i, o] = x[u, i] row_scale[v] g[v, o]                               (E, in * out)
+ * Either may be NULL (not both): without dx, w is not read (and may be NULL); without dw
+ * nothing of size E * in * out is written and x may be NULL. */
+int DGLMINnconvBackward(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* w,
+                        const DGLMIArray* g, const DGLMIArray* row_scale, DGLMIArray* dx,
+                        DGLMIArray* dw, void* stream);
+
 /* _CAPI_DGLRgcnLayer0(G, weight, norm, ret):
  * ret[v, :] = sum_{e=(u->v)} weight[etypes[e], u, :] * norm[e];
  * weight (R, N_src, F), ret (N_dst, F). */
