@@ -2845,6 +2845,44 @@ void gmm_common(const DGLMIGraph* graph, const DGLMICsr& c, const char* which, c
   a.dim = static_cast<int>(mu->shape[1]);
   a.chunk = kGmmChunk;
 }
+
+int64_t numel(const DGLMIArray* t) { return t->shape[0] * feat_numel(t); }
+
+// shapes of an AtomicConv call on the in-CSR: x (N_src, T), dist one float per edge, the
+// three filter parameters K floats each (any shape); fills the walk and the filters of `a`
+void atomic_common(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* dist,
+                   const DGLMIArray* cutoffs, const DGLMIArray* means, const DGLMIArray* scaling,
+                   AtomicArgs& a) {
+  check_graph32(graph, "AtomicConv aggregation");
+  const DGLMICsr& c = graph->in_csr;
+  check_csr(c, "in_csr", true);
+  check_array(x, "x");
+  check_array(dist, "dist");
+  check_array(cutoffs, "cutoffs");
+  check_array(means, "means");
+  check_array(scaling, "scaling");
+  DGLMI_CHECK(x->ndim == 2 && x->shape[0] == c.num_cols, "x must be (source nodes, T)");
+  DGLMI_CHECK(numel(dist) == c.nnz, "dist needs one value per edge");
+  const int64_t K = numel(cutoffs);
+  DGLMI_CHECK(numel(means) == K && numel(scaling) == K,
+              "cutoffs, means and scaling need one value per filter each");
+  DGLMI_CHECK(atomic_ok(K, x->shape[1]), "unsupported AtomicConv shape (DGLMIAtomicOk)");
+  a.indptr = c.indptr;
+  a.rows = c.rows;
+  a.cols = c.indices;
+  a.eids = c.data;
+  a.num_rows = c.num_rows;
+  a.nnz = c.nnz;
+  a.x = x->data;
+  a.dist = dist->data;
+  a.cutoffs = cutoffs->data;
+  a.means = means->data;
+  a.scaling = scaling->data;
+  a.K = static_cast<int>(K);
+  a.T = static_cast<int>(x->shape[1]);
+  a.kp_shift = atomic_kp_shift(K);
+  a.chunk = kAtomicChunk;
+}
 }  // namespace
 
 extern "C" {
@@ -3050,6 +3088,67 @@ int DGLMINnconvBackward(const DGLMIGraph* graph, const DGLMIArray* x, const DGLM
   if (dx != nullptr) lay.point(a, ws.ptr);
   launch_nnconv_backward(a, s);
   check_hip(hipGetLastError(), "NNConv backward launch");
+  API_END();
+}
+
+int DGLMIAtomicOk(int64_t num_filters, int64_t num_channels) {
+  return atomic_ok(num_filters, num_channels) ? 1 : 0;
+}
+int64_t DGLMIAtomicChunk(void) { return kAtomicChunk; }
+
+int DGLMIAtomicAggregate(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* dist,
+                         const DGLMIArray* cutoffs, const DGLMIArray* means,
+                         const DGLMIArray* scaling, DGLMIArray* out, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  AtomicArgs a{};
+  atomic_common(graph, x, dist, cutoffs, means, scaling, a);
+  check_array(out, "out");
+  DGLMI_CHECK(out->ndim == 2 && out->shape[0] == a.num_rows &&
+                  out->shape[1] == static_cast<int64_t>(a.T) * a.K,
+              "out must be (destination nodes, T * K)");
+  a.out = out->data;
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const CarryLayout lay(gmm_chunks(a.nnz), static_cast<int64_t>(a.T) * a.K);
+  Scratch ws(no_workspace(), lay.bytes, s);
+  lay.point(a, ws.ptr);
+  launch_atomic_aggregate(a, s);
+  check_hip(hipGetLastError(), "AtomicConv aggregate launch");
+  API_END();
+}
+
+int DGLMIAtomicEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* g,
+                        const DGLMIArray* dist, const DGLMIArray* cutoffs, const DGLMIArray* means,
+                        const DGLMIArray* scaling, DGLMIArray* ddist, DGLMIArray* dcutoffs,
+                        DGLMIArray* dmeans, DGLMIArray* dscaling, void* stream) {
+  API_BEGIN();
+  DGLMI_CHECK(graph != nullptr, "null graph");
+  AtomicArgs a{};
+  atomic_common(graph, x, dist, cutoffs, means, scaling, a);
+  check_array(g, "g");
+  DGLMI_CHECK(g->ndim == 2 && g->shape[0] == a.num_rows &&
+                  g->shape[1] == static_cast<int64_t>(a.T) * a.K,
+              "g must be (destination nodes, T * K)");
+  a.g = g->data;
+  DGLMIArray* outs[4] = {ddist, dcutoffs, dmeans, dscaling};
+  const char* names[4] = {"ddist", "dcutoffs", "dmeans", "dscaling"};
+  for (int i = 0; i < 4; ++i) {
+    if (outs[i] == nullptr) continue;
+    check_array(outs[i], names[i]);
+    DGLMI_CHECK(numel(outs[i]) == (i == 0 ? a.nnz : a.K),
+                std::string(names[i]) + " must have the size of what it is the gradient of");
+  }
+  a.ddist = ddist ? ddist->data : nullptr;
+  a.dcutoffs = dcutoffs ? dcutoffs->data : nullptr;
+  a.dmeans = dmeans ? dmeans->data : nullptr;
+  a.dscaling = dscaling ? dscaling->data : nullptr;
+  DeviceGuard guard(graph->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Scratch part(no_workspace(), gmm_records(a.nnz) * 3 * a.K * static_cast<int64_t>(sizeof(float)), s);
+  a.part = static_cast<float*>(part.ptr);
+  launch_atomic_edge_grad(a, s);
+  check_hip(hipGetLastError(), "AtomicConv edge gradient launch");
   API_END();
 }
 

@@ -944,6 +944,57 @@ struct NnconvArgs {
 void launch_nnconv_aggregate(const NnconvArgs& a, hipStream_t s);
 void launch_nnconv_backward(const NnconvArgs& a, hipStream_t s);
 
+// AtomicConv's radial-filter aggregation (kernels_atomic.hip):
+//   out[r, t K + k] = sum_{p in row r} x[col_p, t] e_k(dist[eid_p]),
+//   e_k(d) = exp(-scaling[k] (d - means[k])^2) * (d <= cutoffs[k] ? (cos(pi d / cutoffs[k]) + 1) / 2 : 0)
+// over the in-CSR, and the gradients of dist, cutoffs, means and scaling over the same walk.
+// A lane owns a filter; K <= 32 splits the wave into 64 / pow2ceil(K) groups of lanes.
+constexpr int64_t kAtomicChunk = 64;  // positions per wave of the walks (gmm_chunks counts them)
+constexpr int kAtomicMaxK = 256;
+constexpr int kAtomicMaxT = 32;
+inline bool atomic_ok(int64_t K, int64_t T) {
+  return K >= 1 && K <= kAtomicMaxK && T >= 1 && T <= kAtomicMaxT;
+}
+// the instance's accumulators per lane: T rounded up to a power of two
+inline int atomic_tt(int64_t T) {
+  int tt = 1;
+  while (tt < T) tt *= 2;
+  return tt;
+}
+// log2 of the lanes per group: pow2ceil(K), 64 from K = 33 on
+inline int atomic_kp_shift(int64_t K) {
+  int sh = 0;
+  while (sh < 6 && (int64_t(1) << sh) < K) ++sh;
+  return sh;
+}
+struct AtomicArgs {
+  const int32_t* indptr;  // the in-CSR: rows own the output
+  const int32_t* rows;
+  const int32_t* cols;
+  const int32_t* eids;    // edge id per position: dist's index
+  int64_t num_rows, nnz;
+  const float* x;         // (sources, T)
+  const float* dist;      // (E)
+  const float* cutoffs;   // K each
+  const float* means;
+  const float* scaling;
+  int K, T, kp_shift;
+  float* out;             // num_rows x T * K
+  const float* row_scale; // NULL (fixup_float_records reads it)
+  float* carry;           // CarryLayout(gmm_chunks(nnz), T * K)
+  int32_t* seg_cnt;
+  int64_t chunk;          // kAtomicChunk (fixup_role)
+  // k_atomic_edge_grad: g (num_rows, T * K); outputs may be NULL
+  const float* g;
+  float* ddist;           // (E)
+  float* dcutoffs;        // K each
+  float* dmeans;
+  float* dscaling;
+  float* part;            // gmm_records(nnz) x 3 K
+};
+void launch_atomic_aggregate(const AtomicArgs& a, hipStream_t s);
+void launch_atomic_edge_grad(const AtomicArgs& a, hipStream_t s);
+
 // Segment kernels (kernels_segment.hip): rows 0..num_rows-1 of an (N, F) table in
 // position order, segment b = rows offsets[b] .. offsets[b + 1] (a batch of graphs'
 // nodes or edges).  No gather, no index stream.

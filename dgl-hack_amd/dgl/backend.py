@@ -1047,6 +1047,58 @@ def nnconv_aggregate(graph_index, x, w, row_scale=None):
                                   None if row_scale is None else row_scale.contiguous())
 
 
+class _AtomicAggregate(th.autograd.Function):
+    """AtomicConv on kernels_atomic.hip: out[v, t K + k] = sum_e x[u, t]
+    e_k(dist[e]), one k_atomic_aggregate launch on the in-CSR; backward one k_atomic_edge_grad
+    walk for the gradients of dist, cutoffs, means and scaling.  The (E, K) filter values are
+    recomputed, never saved.  x gets no gradient (atomic_route refuses one that asks).
+    Gradients that needs_input_grad does not ask for are not computed."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, dist, cutoffs, means, scaling):
+        out = x.new_empty((gidx.num_dst, x.shape[1] * cutoffs.numel()))
+        K.atomic_aggregate(gidx, x, dist, cutoffs, means, scaling, out)
+        ctx.gidx = gidx
+        ctx.save_for_backward(x, dist, cutoffs, means, scaling)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, dist, cutoffs, means, scaling = ctx.saved_tensors
+        grads = [th.empty_like(t) if need else None
+                 for t, need in zip((dist, cutoffs, means, scaling), ctx.needs_input_grad[2:])]
+        if any(g is not None for g in grads):
+            K.atomic_edge_grad(ctx.gidx, x, grad_out.contiguous(), dist, cutoffs, means, scaling,
+                               *grads)
+        return (None, None) + tuple(grads)
+
+
+def atomic_route(graph, x, dist, num_filters):
+    """The device index when AtomicConv's fused form can run: fp32 2-D device features that
+    do not require grad, one fp32 distance per edge id on the same device, shapes
+    DGLMIAtomicOk serves, and 32-bit CSRs whose edge ids are a permutation of the positions;
+    else None."""
+    if not (isinstance(x, th.Tensor) and x.is_cuda and x.dtype == th.float32 and x.dim() == 2
+            and not x.requires_grad and isinstance(dist, th.Tensor) and dist.device == x.device
+            and dist.dtype == th.float32 and K.atomic_ok(num_filters, x.shape[1])):
+        return None
+    if dist.numel() != graph.number_of_edges():
+        return None
+    gidx = graph._graph.get_immutable_gidx(x.device)
+    if gidx.num_bits != 32 or not gidx.eid_perm or x.shape[0] != gidx.num_src:
+        return None
+    return gidx
+
+
+def atomic_aggregate(graph_index, x, dist, cutoffs, means, scaling):
+    """out[v, t K + k] = sum_{e = (u -> v)} x[u, t] e_k(dist[e]) with e_k(d) = exp(-scaling[k]
+    (d - means[k])^2) (cos(pi d / cutoffs[k]) + 1) / 2 where d <= cutoffs[k], else 0:
+    AtomicConv's radial pooling and sum without the (K, E, 1) filter tensors or the (E, T K)
+    messages.  Differentiable in dist, cutoffs, means and scaling (their shapes are kept)."""
+    return _AtomicAggregate.apply(graph_index, x.contiguous(), dist.contiguous(),
+                                  cutoffs.contiguous(), means.contiguous(), scaling.contiguous())
+
+
 def rgcn_layer0(graph, weight, norm, etypes=None):
     """Layer with one-hot (node id) input: ret[v] = sum_e W[type_e, u] * norm_e.
 

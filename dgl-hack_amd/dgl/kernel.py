@@ -1268,6 +1268,50 @@ def nnconv_backward(graph, x, w, g, row_scale, dx=None, dw=None):
         _arr(dx, "dx"), _arr(dw, "dw"), _stream(g)))
 
 
+# ---- AtomicConv's radial-filter aggregation (kernels_atomic.hip) -------------------------------
+# positions per wave of the walks (internal.h kAtomicChunk; checked against the library)
+ATOMIC_CHUNK = 64
+
+
+def atomic_ok(num_filters, num_channels):
+    """DGLMIAtomicOk: the shapes the AtomicConv kernels serve (1 to 256 radial filters, 1 to 32
+    feature channels), asked of the library."""
+    return bool(_ffi.lib().DGLMIAtomicOk(int(num_filters), int(num_channels)))
+
+
+def _atomic_call(graph, tensors):
+    _check_ctx(graph, tensors)
+    if _ffi.lib().DGLMIAtomicChunk() != ATOMIC_CHUNK:
+        raise DGLError("kernel.ATOMIC_CHUNK differs from the library's")
+    if not graph.eid_perm:
+        raise DGLError("the AtomicConv kernels index the distances by edge id: the graph's edge "
+                       "ids must be a permutation of its positions")
+    return graph.cstruct()
+
+
+def atomic_aggregate(graph, x, dist, cutoffs, means, scaling, out):
+    """DGLMIAtomicAggregate: out[v, t K + k] = sum_{e = (u -> v)} x[u, t] e_k(dist[e]) over the
+    in-CSR; x (N_src, T), dist one float per edge id, K floats per parameter, out (N_dst, T K)."""
+    g = _atomic_call(graph, [("x", x), ("dist", dist), ("cutoffs", cutoffs), ("means", means),
+                             ("scaling", scaling), ("out", out)])
+    check_call(_ffi.lib().DGLMIAtomicAggregate(
+        ctypes.byref(g), _arr(x, "x"), _arr(dist, "dist"), _arr(cutoffs, "cutoffs"),
+        _arr(means, "means"), _arr(scaling, "scaling"), _arr(out, "out"), _stream(out)))
+
+
+def atomic_edge_grad(graph, x, g, dist, cutoffs, means, scaling, ddist=None, dcutoffs=None,
+                     dmeans=None, dscaling=None):
+    """DGLMIAtomicEdgeGrad: the gradients of dist, cutoffs, means and scaling (each optional,
+    None is not computed) from g (N_dst, T K), the gradient of atomic_aggregate's output."""
+    gr = _atomic_call(graph, [("x", x), ("g", g), ("dist", dist), ("cutoffs", cutoffs),
+                              ("means", means), ("scaling", scaling), ("ddist", ddist),
+                              ("dcutoffs", dcutoffs), ("dmeans", dmeans), ("dscaling", dscaling)])
+    check_call(_ffi.lib().DGLMIAtomicEdgeGrad(
+        ctypes.byref(gr), _arr(x, "x"), _arr(g, "g"), _arr(dist, "dist"), _arr(cutoffs, "cutoffs"),
+        _arr(means, "means"), _arr(scaling, "scaling"), _arr(ddist, "ddist"),
+        _arr(dcutoffs, "dcutoffs"), _arr(dmeans, "dmeans"), _arr(dscaling, "dscaling"), _stream(g)))
+
+
 # ---- segment kernels (batched graphs: dgl.readout, dgl.nn.pytorch.glob) -------------------
 class Segments:
     """The row segments of a batch for the DGLMISegment* entries: ``offsets`` a device

@@ -1,8 +1,8 @@
 """PyTorch modules (``dgl.nn.pytorch``)."""
 from .conv import (GraphConv, GATConv, FusedGATConv, RelGraphConv, SAGEConv,  # noqa: F401
                    GINConv, SGConv, APPNPConv, TAGConv, ChebConv, AGNNConv, EdgeConv,
-                   GatedGraphConv, GMMConv, NNConv, DenseGraphConv,
-                   DenseSAGEConv, DenseChebConv)
+                   GatedGraphConv, GMMConv, NNConv, AtomicConv, RadialPooling, CFConv,
+                   ShiftedSoftplus, DenseGraphConv, DenseSAGEConv, DenseChebConv)
 from .softmax import edge_softmax  # noqa: F401
 from .glob import (SumPooling, AvgPooling, MaxPooling, SortPooling,  # noqa: F401
                    GlobalAttentionPooling, Set2Set, WeightAndSum)

@@ -14,4 +14,6 @@ from .edgeconv import EdgeConv  # noqa: F401
 from .gatedgraphconv import GatedGraphConv  # noqa: F401
 from .gmmconv import GMMConv  # noqa: F401
 from .nnconv import NNConv  # noqa: F401
+from .atomicconv import AtomicConv, RadialPooling  # noqa: F401
+from .cfconv import CFConv, ShiftedSoftplus  # noqa: F401
 from .dense import DenseGraphConv, DenseSAGEConv, DenseChebConv  # noqa: F401

@@ -772,6 +772,38 @@ int DGLMINnconvBackward(const DGLMIGraph* graph, const DGLMIArray* x, const DGLM
                         const DGLMIArray* g, const DGLMIArray* row_scale, DGLMIArray* dx,
                         DGLMIArray* dw, void* stream);
 
+/* ---- AtomicConv (ACNN): radial-filter aggregation (extension; the reference builds
+ * three (K, E, 1) filter tensors, an (E, T K) message tensor and reduces it on degree
+ * buckets, atomicconv.py:55-116).  Here the filters are computed where they are used:
+ *   out[v, t K + k] = sum_{e = (u -> v)} x[u, t] e_k(dist[e])
+ *   e_k(d) = h_k(d) f_k(d),  h_k(d) = exp(-scaling[k] (d - means[k])^2)
+ *   f_k(d) = 1/2 (cos(pi d / cutoffs[k]) + 1) if d <= cutoffs[k], else 0
+ * over the in-CSR.  x (N_src, T), dist one float per edge id, cutoffs / means / scaling K
+ * floats each (any shape), out (N_dst, T * K), overwritten, rows without in-edges with
+ * zeros.  The (E, K) filter values are never stored: DGLMIAtomicEdgeGrad recomputes them
+ * with the same operations.  fp32, 32-bit graphs, no floating-point atomics: bit-identical
+ * from run to run.
+ * DGLMIAtomicOk(K, T): the shapes served (K 1 .. 256, T 1 .. 32).
+ * DGLMIAtomicChunk(): CSR positions per wave of the walks. */
+int DGLMIAtomicOk(int64_t num_filters, int64_t num_channels);
+int64_t DGLMIAtomicChunk(void);
+int DGLMIAtomicAggregate(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* dist,
+                         const DGLMIArray* cutoffs, const DGLMIArray* means,
+                         const DGLMIArray* scaling, DGLMIArray* out, void* stream);
+/* Gradients over the in-CSR from g (N_dst, T * K), the gradient of DGLMIAtomicAggregate's
+ * output; c, r, gamma = cutoffs, means, scaling:
+ *   dw_k(e) = sum_t x[src(e), t] g[dst(e), t K + k],  d = dist[e],  s_k = 1/2 sin(pi d / c_k)
+ *   dscaling[k] = sum_e dw_k (-(d - r_k)^2) e_k
+ *   dmeans[k]   = sum_e dw_k 2 gamma_k (d - r_k) e_k
+ *   dcutoffs[k] = sum_e dw_k h_k s_k pi d / c_k^2                       (d <= c_k, else 0)
+ *   ddist[e]    = sum_k dw_k (-2 gamma_k (d - r_k) e_k - h_k s_k pi / c_k)   every edge id once
+ * Any output may be NULL and is then not computed; the others are overwritten.  The
+ * gradient of x is not served. */
+int DGLMIAtomicEdgeGrad(const DGLMIGraph* graph, const DGLMIArray* x, const DGLMIArray* g,
+                        const DGLMIArray* dist, const DGLMIArray* cutoffs, const DGLMIArray* means,
+                        const DGLMIArray* scaling, DGLMIArray* ddist, DGLMIArray* dcutoffs,
+                        DGLMIArray* dmeans, DGLMIArray* dscaling, void* stream);
+
 /* _CAPI_DGLRgcnLayer0(G, weight, norm, ret):
  * ret[v, :] = sum_{e=(u->v)} weight[etypes[e], u, :] * norm[e];
  * weight (R, N_src, F), ret (N_dst, F). */
